@@ -10,6 +10,11 @@ reduction talk across ranks.
 
 Prints ONE JSON line on rank 0.  --config selects another BASELINE config
 for DESIGN.md numbers (c3 mixed, c4 SHA-512, e2e host-memory path).
+
+A plain run sets up, warms up, times the steps and prints the line.  --full
+adds what takes runs of its own: the CPU baseline of C2 / C3 / C4 and, on
+the default config, the other BASELINE configs in `extra_configs`.
+--dump-outputs DIR writes what the last timed step computed as .npy files.
 """
 from __future__ import annotations
 
@@ -82,6 +87,8 @@ ALG_NAMES = {1: "SHA-256", 2: "SHA-384", 3: "SHA-512", 4: "HMAC-SHA256",
              5: "HMAC-SHA384", 6: "HMAC-SHA512"}
 HMAC_KEY = bytes(range(64))
 EVENT_EVERY = 4     # event pair around every 4th timed step (kernel duration)
+DUMP_BUDGET = 32 << 20      # bytes of float32 --dump-outputs writes, all arrays
+DUMP_SEED = 0               # row sample of an output larger than its share
 
 
 def dist_env():
@@ -426,11 +433,59 @@ def device_step(name, inp, out, ws_buf, stream, unbinned=False, kind=None):
                                     binned=not unbinned, stream=stream)
 
 
+def step_outputs(cfg, inp, out):
+    """The arrays a caller of the config's step receives, by name."""
+    kind = cfg["kind"]
+    if kind == "burst_rx":
+        return {"result": out, "iv": inp["iv"], "seq": inp["oseq"],
+                "flags": inp["oflags"]}
+    if kind == "burst_tx":      # header and HMAC field sealed in place
+        return {"result": out, "datagrams": inp["data"]}
+    if kind == "dgram_verify":
+        return {"result": out}
+    return {"iv" if kind == "ph_iv" else "digests": out}
+
+
+def sample_outputs(outputs):
+    """Host copies of the step's outputs, bytes as float32 and 32-bit words
+    as float64 (both exact), DUMP_BUDGET bytes in all: an array over its
+    equal share is cut to a seeded sample of its rows in ascending order (a
+    flat byte buffer counts as rows of 256 bytes), the same rows in every
+    run of the same arguments."""
+    import numpy as np
+    import torch
+    share = DUMP_BUDGET // len(outputs)
+    got = {}
+    for key, t in outputs.items():
+        dt = np.float32 if t.dtype == torch.uint8 else np.float64
+        size = np.dtype(dt).itemsize
+        if t.dim() == 1 and t.dtype == torch.uint8 and t.numel() * size > share:
+            t = t[:t.numel() // 256 * 256].view(-1, 256)
+        row = t[0].numel() if t.dim() > 1 else 1
+        keep = share // (size * row)
+        if t.shape[0] > keep:
+            rows = np.sort(np.random.default_rng(DUMP_SEED).choice(
+                t.shape[0], keep, replace=False))
+            t = t[torch.from_numpy(rows).to(t.device)]
+        got[key] = t.cpu().numpy().astype(dt)
+    return got
+
+
+def write_outputs(path, arrays, rank=0):
+    """DIR/<name>.npy on rank 0, DIR/<name>.rank<k>.npy on the others."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for key, a in arrays.items():
+        np.save(os.path.join(path, key + (f".rank{rank}" if rank else "") + ".npy"), a)
+
+
 def time_device_config(name, dev, steps, warmup, prewarm_ms, ws=1, rank=0,
-                       dist_backend="nccl", unbinned=False, clock_probe=None):
+                       dist_backend="nccl", unbinned=False, clock_probe=None,
+                       keep_outputs=False):
     """Untimed clock ramp and warmup, then exactly `steps` steps between
     barriers + synchronize; the dominant kernel's duration from HIP events
-    on the launch stream.  Returns the measurements (max over ranks)."""
+    on the launch stream.  Returns the measurements (max over ranks), with
+    keep_outputs also the last step's outputs (sample_outputs)."""
     import torch
     import torch.distributed as dist
     from ilias_net2_amd import batch, _lib
@@ -534,6 +589,8 @@ def time_device_config(name, dev, steps, warmup, prewarm_ms, ws=1, rank=0,
            "per_launch_bytes": per_launch,
            "sclk_during_mhz": (round(sum(samples) / len(samples)) if samples else None),
            "sclk_samples": len(samples), "sclk_min_mhz": min(samples) if samples else None}
+    if keep_outputs:
+        res["outputs"] = sample_outputs(step_outputs(cfg, inp, out))
     del inp, out, ws_buf
     torch.cuda.empty_cache()
     return res
@@ -733,14 +790,27 @@ def main():
                          "reaches its steady-state clock (a cold MI355X runs "
                          "the first ~50 launches ~15%% slower)")
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS) + ["e2e", "c1"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also what takes runs of its own: the CPU baseline "
+                         "(c2, c3, c4) and, on c2, the extra BASELINE configs "
+                         "(C1, C3, C4, end to end) in the same line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps write what the last one computed "
+                         "as DIR/<name>.npy (bytes as float32, words as float64; a "
+                         "seeded row sample of an output over its share of 32 MiB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full without the CPU baseline")
     ap.add_argument("--no-extras", action="store_true",
-                    help="c2 at N=1: skip the extra BASELINE configs (C1, C3, C4, "
-                         "end to end) that otherwise ride in the same line")
+                    help="--full on c2 without the extra BASELINE configs")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"])
     ap.add_argument("--unbinned", action="store_true",
                     help="c3: hash in submission order (ablation)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.config in ("e2e", "c1"):
+        ap.error("--dump-outputs covers the device-resident configs, not "
+                 + args.config)
 
     import torch
     import torch.distributed as dist
@@ -772,7 +842,10 @@ def main():
     name = args.config
     cfg = CONFIGS[name]
     r = time_device_config(name, dev, args.steps, args.warmup, args.prewarm_ms,
-                           ws, rank, args.dist_backend, args.unbinned, probe)
+                           ws, rank, args.dist_backend, args.unbinned, probe,
+                           keep_outputs=bool(args.dump_outputs))
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, r.pop("outputs"), rank)
     value = r["n"] * ws / (r["ms_per_step"] / 1e3)
     roof, valu = rooflines(name, r["launch_ms"], r["per_launch_bytes"],
                            r["sclk_during_mhz"])
@@ -808,11 +881,11 @@ def main():
         line.update(sf)
         line["config"]["parallelism"] = (
             f"{ws} independent shards, no collective; " + sf["device_sharing"])
-    if name == "c2" and not args.no_extras:
+    if args.full and name == "c2" and not args.no_extras:
         line["extra_configs"] = extra_configs(
             args, dev, probe, ws, rank,
             label=devices_label(ws, line.get("distinct_devices", ws)))
-    if not args.no_cpu_baseline and name in ("c2", "c3", "c4"):
+    if args.full and not args.no_cpu_baseline and name in ("c2", "c3", "c4"):
         cb = cpu_baseline_after_gpu(cfg, rank, ws)
         if rank == 0:
             line["cpu_baseline"] = cb

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The driver's bench command under rocprofv3 --kernel-trace --stats: the
+"""The default bench line (--full) under rocprofv3 --kernel-trace --stats: the
 dominant kernels' trace averages next to the line's own HIP-event kernel
 times (tools/gpu_round_final.sh STAGE=trace_default).
   default_trace_summary.py KERNEL_STATS_CSV BENCH_LOG [KERNEL_TRACE_CSV]
@@ -24,7 +24,7 @@ def main():
         if ln.startswith("{"):
             line = json.loads(ln)
     out = {"command": "rocprofv3 --kernel-trace --stats -- python3 bench.py --gpus 1 "
-                      "--steps 20 --warmup 5 (the driver's N=1 command)",
+                      "--steps 20 --warmup 5 --full (the N=1 line with its extra_configs)",
            "line_value_digests_per_s": line and line["value"],
            "line_kernel_ms_hip_events": line and line["roofline"]["kernel_ms"],
            "line_extra_kernel_ms": line and {k: (v.get("roofline") or {}).get("kernel_ms")
