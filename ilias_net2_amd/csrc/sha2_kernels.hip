@@ -966,13 +966,33 @@ struct HMid {
 	uint32_t w[4][16];
 };
 
+/*
+ * Where a lane's two midstates come from (hmac_lane's MIDS): inner() before
+ * the block loop, outer() after it.  LdsMids: the launch's one key, in the
+ * workgroup's LDS copy.
+ */
+struct LdsMids {
+	const uint32_t (*mid)[16];
+	template <class H>
+	__device__ __forceinline__ void inner(typename H::State &st) const
+	{
+		load_mid<H>(mid, 0, st);
+	}
+	template <class H>
+	__device__ __forceinline__ void outer(typename H::State &st) const
+	{
+		load_mid<H>(mid, 1, st);
+	}
+};
+
 /* Inner hash from the ipad midstate, one address mode. */
-template <class H, int AMODE, bool PADCONST, bool PREFETCH = H::PREFETCH>
+template <class H, int AMODE, bool PADCONST, class MIDS,
+    bool PREFETCH = H::PREFETCH>
 __device__ __forceinline__ void hmac_inner(const uint8_t *p, uint32_t len,
-    const uint32_t (*mid)[16], const typename H::word *kw,
+    const MIDS &mids, const typename H::word *kw,
     typename H::State &st, bool padtab)
 {
-	load_mid<H>(mid, 0, st);
+	mids.template inner<H>(st);
 	absorb<H, AMODE, PREFETCH>(p, len, st);
 	if (!PADCONST && padtab)
 		finish<H, true>(p, len, 0, kw, st);
@@ -981,20 +1001,21 @@ __device__ __forceinline__ void hmac_inner(const uint8_t *p, uint32_t len,
 		    st);
 }
 
-template <class H, bool PADCONST>
+template <class H, bool PADCONST, class MIDS>
 __device__ __forceinline__ void hmac_lane(const uint8_t *p, uint32_t len,
-    int is384, int amode, const uint32_t (*mid)[16],
+    int is384, int amode, const MIDS &mids,
     const typename H::word *kw, typename H::State &st, bool padtab = false)
 {
 	constexpr int NW32 = H::NW32;
-	/* the midstates stay in LDS and are read where they are used, so
-	 * neither is held in VGPRs across the block loop */
+	/* the midstates stay in LDS (the key table: in global memory) and are
+	 * read where they are used, so neither is held in VGPRs across the
+	 * block loop */
 	if (amode == AMODE_A16)
-		hmac_inner<H, AMODE_A16, PADCONST>(p, len, mid, kw, st, padtab);
+		hmac_inner<H, AMODE_A16, PADCONST>(p, len, mids, kw, st, padtab);
 	else if (amode == AMODE_A4)
-		hmac_inner<H, AMODE_A4, PADCONST>(p, len, mid, kw, st, padtab);
+		hmac_inner<H, AMODE_A4, PADCONST>(p, len, mids, kw, st, padtab);
 	else
-		hmac_inner<H, AMODE_A1, PADCONST>(p, len, mid, kw, st, padtab);
+		hmac_inner<H, AMODE_A1, PADCONST>(p, len, mids, kw, st, padtab);
 
 	/* outer: one block = inner digest || 0x80 || 0... || bit count */
 	uint32_t w[NW32];
@@ -1010,7 +1031,7 @@ __device__ __forceinline__ void hmac_lane(const uint8_t *p, uint32_t len,
 	const uint64_t obits = (uint64_t)(H::BLOCK + 4 * dw) << 3;
 	w[NW32 - 2] = (uint32_t)(obits >> 32);
 	w[NW32 - 1] = (uint32_t)obits;
-	load_mid<H>(mid, 1, st);
+	mids.template outer<H>(st);
 	H::compress(st, w);
 }
 
@@ -1033,7 +1054,7 @@ __device__ __forceinline__ void hmac_lane(const uint8_t *p, uint32_t len,
  *                 2 if the datagram is shorter than dlen (:240-244).
  */
 enum { HMAC_DIGESTS = 0, HMAC_SIGN = 1, HMAC_VERIFY = 2, HMAC_BURST_RX = 3,
-    HMAC_BURST_TX = 4 };
+    HMAC_BURST_TX = 4, HMAC_BURST_RX_MC = 5, HMAC_BURST_TX_MC = 6 };
 
 /*
  * Packet-burst codes (the burst kernels below): the status byte is the
@@ -1041,6 +1062,9 @@ enum { HMAC_DIGESTS = 0, HMAC_SIGN = 1, HMAC_VERIFY = 2, HMAC_BURST_RX = 3,
  * datagram's region decides it.
  */
 #define BURST_VERIFY 0x80u
+/* (HMAC_BURST_RX_MC only) | BURST_NOIV: the datagram's connection has no
+ * cipher key, so no IV is due whatever its flags say */
+#define BURST_NOIV 0x40u
 #define PKT_PH_ENCRYPTED 0x00000001u	/* types/packet.n2t:27 */
 #define PKT_PH_SIGNED 0x00000002u	/* types/packet.n2t:28 */
 #define PKT_PH_ALTKEY 0x80000000u	/* types/packet.n2t:34 */
@@ -1073,6 +1097,113 @@ __device__ __forceinline__ uint32_t load_be32_bytes(const uint8_t *p)
  */
 /* (struct BurstArgs: sha2_launch.h) */
 
+/*
+ * HMAC_BURST_RX_MC / HMAC_BURST_TX_MC: the same per lane under the keys of
+ * the datagram's own connection (net2_packet_{decode,encode}_burst_mc): a
+ * shared socket's receive batch interleaves the datagrams of many
+ * connections (src/udp_connection.c:81-170), each with its own negotiated
+ * key and rollover state.  Datagram i belongs to slot kt.conn[i] of the
+ * device key table (Net2KeyEnt, sha2_launch.h); the entry's bits, cutoff and
+ * rx_start stand in for BurstArgs' and its midstates for the launch's, read
+ * from global memory where they are used.  RX: the header is decoded first
+ * (a runt is PKT_BAD whatever its connection, packet.n2t:196-198 precede the
+ * key lookup at :210), then a datagram without a connection -- conn[i] out
+ * of range or the slot's rx side unset -- is PKT_NOCONN: header stored, no
+ * hash, no IV.  TX: a slot without a tx side is PKT_NOCONN and left
+ * untouched.  An index out of range is clamped to entry 0 before any
+ * address is formed from it.
+ */
+#define PKT_NOCONN 5			/* NET2_PBURST_NOCONN */
+
+/* The entry of datagram i; *in: its index was in range (else entry 0). */
+__device__ __forceinline__ const Net2KeyEnt *keytab_ent(const KeyTabArgs &kt,
+    uint64_t i, bool *in)
+{
+	const uint32_t c = kt.conn[i];
+	*in = c < kt.slots;
+	return kt.tab + (*in ? c : 0u);
+}
+
+/* net2_ck_rx_key (src/conn_keys.c:447-476) over an entry's meta words. */
+__device__ __forceinline__ bool keytab_rx_alt(uint32_t bits, uint32_t cutoff,
+    uint32_t rx_start, uint32_t seq, uint32_t fl)
+{
+	return (bits & NET2_KT_RX_ALT) != 0 && ((fl & PKT_PH_ALTKEY) != 0 ||
+	    ((bits & NET2_KT_RX_NOCUT) == 0 &&
+	    seq - rx_start >= cutoff - rx_start));
+}
+
+/* A table midstate (16-byte aligned) into a state: dwordx4 global loads. */
+template <class H>
+__device__ __forceinline__ void load_mid_tab(const uint32_t *m,
+    typename H::State &st)
+{
+	typedef __attribute__((address_space(1))) const u32x4 gconst_u32x4;
+	gconst_u32x4 *q = (gconst_u32x4 *)reinterpret_cast<uintptr_t>(m);
+	constexpr int NQ = sizeof(typename H::word) == 4 ? 2 : 4;
+	u32x4 v[NQ];
+#pragma unroll
+	for (int k = 0; k < NQ; k++)
+		v[k] = q[k];
+#pragma unroll
+	for (int k = 0; k < NQ; k++) {
+		if (sizeof(typename H::word) == 4) {
+			st[4 * k] = v[k].x;
+			st[4 * k + 1] = v[k].y;
+			st[4 * k + 2] = v[k].z;
+			st[4 * k + 3] = v[k].w;
+		} else {
+			st[2 * k] = mk64(v[k].y, v[k].x);
+			st[2 * k + 1] = mk64(v[k].w, v[k].z);
+		}
+	}
+}
+
+/*
+ * hmac_lane's midstates from the key table.  in: the inner midstate, chosen
+ * by hmac_item before the hash.  The outer one is found again from conn[i]
+ * after the block loop -- for RX with the key choice redone from the stored
+ * header -- as the hash field is from offsets[i], so no entry address is
+ * held in VGPRs across the loop.
+ */
+template <bool RX>
+struct TabMids {
+	const KeyTabArgs &kt;
+	const BurstArgs &rx;
+	uint64_t i;
+	const uint32_t *in;
+	template <class H>
+	__device__ __forceinline__ void inner(typename H::State &st) const
+	{
+		load_mid_tab<H>(in, st);
+	}
+	template <class H>
+	__device__ __forceinline__ void outer(typename H::State &st) const
+	{
+		/* an opaque copy of i: these are addresses and loads of their
+		 * own, not hmac_item's (&conn[i] would stay live across the hash) */
+		uint64_t j = i;
+		/* the look-up and its loads stay between the inner digest and the
+		 * outer compression: hoisted to hide their latency, the 8 to 16
+		 * midstate VGPRs would be live with the outer block's schedule
+		 * (the SHA-512 TX instance: 124 VGPRs against 97) */
+		__builtin_amdgcn_sched_barrier(0);
+		asm volatile("" : "+v"(j));
+		bool inr;
+		const Net2KeyEnt *e = keytab_ent(kt, j, &inr);
+		const uint32_t *m = e->tx[1];
+		if (RX) {
+			const uint4 mt = *reinterpret_cast<const uint4 *>(e->meta);
+			m = e->rx[keytab_rx_alt(mt.x, mt.y, mt.z, rx.seq[j],
+			    rx.flags[j]) ? 3 : 1];
+		}
+		load_mid_tab<H>(m, st);
+#pragma unroll
+		for (int k = 0; k < 8; k++)
+			asm volatile("" : "+v"(st[k]));
+		__builtin_amdgcn_sched_barrier(0);
+	}
+};
 
 
 /*
@@ -1090,11 +1221,17 @@ __device__ __forceinline__ void hmac_item(uint64_t g,
     const uint32_t *__restrict__ lens, const uint32_t *__restrict__ perm,
     uint64_t stride, uint32_t fixed_len, uint64_t n,
     uint8_t *__restrict__ out, const PadKW<typename H::word> &pad,
-    const BurstArgs &rx, const uint32_t (*mid)[16])
+    const BurstArgs &rx, const uint32_t (*mid)[16],
+    const KeyTabArgs &kt = KeyTabArgs{})
 {
 	constexpr int is384 = IS384;
 	constexpr uint32_t dlen = sizeof(typename H::word) == 4 ? 32 :
 	    IS384 ? 48 : 64;
+	/* the multi-connection modes: keys per lane from the table kt (mid
+	 * unused, no rec form) */
+	constexpr bool MC = MODE == HMAC_BURST_RX_MC || MODE == HMAC_BURST_TX_MC;
+	constexpr bool RXM = MODE == HMAC_BURST_RX || MODE == HMAC_BURST_RX_MC;
+	constexpr bool TXM = MODE == HMAC_BURST_TX || MODE == HMAC_BURST_TX_MC;
 	const uint32_t (*lmid)[16] = mid;	/* this lane's key */
 	const bool live = g < n;
 	uint64_t i = g;
@@ -1116,19 +1253,29 @@ __device__ __forceinline__ void hmac_item(uint64_t g,
 	 * +0, then header, datagram index and code -- so a wave's stores cover
 	 * one contiguous stretch of (host) memory; the address is formed where
 	 * it is used, not held across the hash */
-	if (MODE == HMAC_BURST_TX) {
+	if (TXM) {
 		if (live) {
 			rx_seq = rx.seq[i];
 			rx_fl = rx.flags[i];
 		}
 		const bool sg = (rx_fl & PKT_PH_SIGNED) != 0;
 		const bool cr = (rx_fl & PKT_PH_ENCRYPTED) != 0;
-		if (!sg || cr != (rx.enc_set != 0))
+		uint32_t bits = 0;	/* MC: the connection's entry */
+		if (MC) {
+			bool inr;
+			const Net2KeyEnt *e = keytab_ent(kt, i, &inr);
+			bits = inr ? e->meta[0] : 0u;
+			lmid = e->tx;
+		}
+		if (MC && (bits & NET2_KT_TX) == 0)
+			rx_st = PKT_NOCONN;	/* the slot has no tx key */
+		else if (!sg || cr != (MC ? (bits & NET2_KT_TX_ENC) != 0 :
+		    rx.enc_set != 0))
 			rx_st = PKT_UNSAFE;
 		else if (len < 8 + dlen)
 			rx_st = PKT_RESOURCE;	/* no room for header and hash */
 		const bool ok = live && rx_st == PKT_OK;
-		if (live && rx.rec != nullptr) {
+		if (live && !MC && rx.rec != nullptr) {
 			*reinterpret_cast<uint4 *>(rx.rec + g * (dlen + 16) + dlen) =
 			    make_uint4(ok ? bswap32(rx_seq) : 0u,
 			    ok ? bswap32(rx_fl) : 0u, (uint32_t)i, rx_st);
@@ -1146,29 +1293,48 @@ __device__ __forceinline__ void hmac_item(uint64_t g,
 		} else {
 			len = 0;
 		}
-		if (live && rx.rec == nullptr)
+		if (live && (MC || rx.rec == nullptr))
 			rx.status[i] = (uint8_t)rx_st;
 	}
-	if (MODE == HMAC_BURST_RX) {
+	if (RXM) {
 		if (len < 8) {
 			rx_st = PKT_BAD;	/* header decode fails */
 		} else {
 			rx_seq = load_be32_bytes(p);
 			rx_fl = load_be32_bytes(p + 4);
 		}
-		/* net2_ck_rx_key (src/conn_keys.c:447-476): the alternate key
-		 * when the datagram says so or lies past the cutoff */
-		const bool use_alt = rx_st == PKT_OK && rx.alt &&
-		    ((rx_fl & PKT_PH_ALTKEY) != 0 || (!rx.no_cutoff &&
-		    rx_seq - rx.rx_start >= rx.cutoff - rx.rx_start));
-		if (use_alt)
-			lmid = mid + 2;
-		const int enc_set = use_alt ? rx.alt_enc_set : rx.enc_set;
+		bool use_alt;
+		int enc_set;
+		if (MC) {
+			/* the connection's entry, looked up once the header is
+			 * decoded (packet.n2t:210) */
+			bool inr;
+			const Net2KeyEnt *e = keytab_ent(kt, i, &inr);
+			const uint4 mt = *reinterpret_cast<const uint4 *>(e->meta);
+			const uint32_t bits = inr ? mt.x : 0u;
+			use_alt = rx_st == PKT_OK &&
+			    keytab_rx_alt(bits, mt.y, mt.z, rx_seq, rx_fl);
+			lmid = e->rx + (use_alt ? 2 : 0);
+			enc_set = (bits & NET2_KT_RX_ENC) != 0;
+			if (rx_st == PKT_OK && (bits & NET2_KT_RX) == 0)
+				rx_st = PKT_NOCONN;	/* no rx key: nothing hashed */
+		} else {
+			/* net2_ck_rx_key (src/conn_keys.c:447-476): the alternate
+			 * key when the datagram says so or lies past the cutoff */
+			use_alt = rx_st == PKT_OK && rx.alt &&
+			    ((rx_fl & PKT_PH_ALTKEY) != 0 || (!rx.no_cutoff &&
+			    rx_seq - rx.rx_start >= rx.cutoff - rx.rx_start));
+			if (use_alt)
+				lmid = mid + 2;
+			enc_set = use_alt ? rx.alt_enc_set : rx.enc_set;
+		}
 		if (rx_st == PKT_OK && ((rx_fl & PKT_PH_SIGNED) == 0 ||
 		    (enc_set && (rx_fl & PKT_PH_ENCRYPTED) == 0)))
 			rx_st = PKT_UNSAFE;
 		if (rx_st == PKT_OK) {
 			rx_st |= BURST_VERIFY;	/* hash field || payload */
+			if (MC && !enc_set)
+				rx_st |= BURST_NOIV;
 			p += 8;
 			len -= 8;
 		} else {
@@ -1205,8 +1371,13 @@ __device__ __forceinline__ void hmac_item(uint64_t g,
 	 * pays only when a whole workgroup's inner lengths are one multiple of
 	 * 128 bytes, which no MTU mix has: payload + 128-byte key block of
 	 * {64, 512, 1428 / 1500} B.) */
-	hmac_lane<H, PADCONST>(p, len, is384, amode, lmid,
-	    kw != nullptr ? kw : pad.kw, st, padtab);
+	if constexpr (MC)
+		hmac_lane<H, PADCONST>(p, len, is384, amode,
+		    TabMids<RXM>{ kt, rx, i, lmid[0] },
+		    kw != nullptr ? kw : pad.kw, st, padtab);
+	else
+		hmac_lane<H, PADCONST>(p, len, is384, amode, LdsMids{ lmid },
+		    kw != nullptr ? kw : pad.kw, st, padtab);
 	materialize<H>(st);
 	if (!live)
 		return;
@@ -1219,9 +1390,8 @@ __device__ __forceinline__ void hmac_item(uint64_t g,
 	 * profiles/pmc_burst_rx.json): HBM bytes, no time on this VALU-bound
 	 * kernel */
 	const uint8_t *field = MODE == HMAC_DIGESTS ? nullptr :
-	    base + offsets[i] + (MODE == HMAC_BURST_RX || MODE == HMAC_BURST_TX ?
-	    8 : 0);
-	if (MODE == HMAC_VERIFY || MODE == HMAC_BURST_RX) {
+	    base + offsets[i] + (RXM || TXM ? 8 : 0);
+	if (MODE == HMAC_VERIFY || RXM) {
 		/* o[] holds the digest bytes little-endian per word, the order
 		 * store_digest writes them in */
 		uint32_t diff = 0;
@@ -1252,7 +1422,7 @@ __device__ __forceinline__ void hmac_item(uint64_t g,
 		out[i] = short_dgram ? 2 : diff != 0;
 		return;
 	}
-	constexpr bool SIGNS = MODE == HMAC_SIGN || MODE == HMAC_BURST_TX;
+	constexpr bool SIGNS = MODE == HMAC_SIGN || TXM;
 	if (SIGNS && short_dgram)
 		return;
 	if (MODE == HMAC_BURST_TX && rx.rec != nullptr)
@@ -1304,6 +1474,70 @@ __global__ __launch_bounds__(256) void hmac_kernel(const uint8_t *__restrict__ b
 	hmac_item<H, PADCONST, MODE, IS384>(g, base, offsets, lens,
 	    offsets != nullptr ? bin_perm(ws, launch) : nullptr, stride,
 	    fixed_len, n, out, pad, rx, mid);
+}
+
+/*
+ * hmac_kernel's sibling for the multi-connection burst modes
+ * (HMAC_BURST_RX_MC / _TX_MC, variable layout): the same hmac_item, no key
+ * in the arguments and none in LDS -- lane by lane from the key table.
+ */
+template <class H, int MODE, bool IS384>
+__global__ __launch_bounds__(256) void hmac_mc_kernel(
+    const uint8_t *__restrict__ base, const uint64_t *__restrict__ offsets,
+    const uint32_t *__restrict__ lens, const uint32_t *__restrict__ ws,
+    uint32_t launch, uint64_t n, uint8_t *__restrict__ out,
+    const uint32_t *__restrict__ conn, const Net2KeyEnt *__restrict__ tab,
+    uint32_t slots, PadKW<typename H::word> pad, BurstArgs rx)
+{
+	const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (sizeof(typename H::word) == 8)
+		k512_lds_fill();	/* (synchronises the workgroup) */
+	const KeyTabArgs kt = { conn, tab, slots };
+	hmac_item<H, false, MODE, IS384>(g, base, offsets, lens,
+	    bin_perm(ws, launch), 0, 0, n, out, pad, rx, nullptr, kt);
+}
+
+/*
+ * One slot's update (net2_burst_keytab_set_rx / _set_tx / _clear): the new
+ * midstates and meta words arrive by value and one wave stores them, 16
+ * bytes per lane (the argument is read with constant indices only and
+ * selected per lane: a dynamic index would copy it to scratch).  side
+ * NET2_KT_RX writes the rx midstates, cutoff and rx_start and replaces the
+ * rx bits; NET2_KT_TX the tx midstates and the tx bits; 0 clears every bit.
+ * Stream order is the only synchronisation an entry has.
+ */
+__global__ __launch_bounds__(64) void keytab_set_kernel(Net2KeyEnt *ent,
+    uint32_t side, uint32_t bits, uint32_t cutoff, uint32_t rx_start, HMid hm)
+{
+	if (blockIdx.x != 0)
+		return;
+	const unsigned t = threadIdx.x;
+	uint4 *q = reinterpret_cast<uint4 *>(ent);
+	/* lane t < 16: the t-th 16 bytes of hm (rx: all four midstates, q[1..16];
+	 * tx: the first two, q[17..24]) */
+	uint4 v = make_uint4(0, 0, 0, 0);
+#pragma unroll
+	for (int k = 0; k < 16; k++)
+		if (t == (unsigned)k)
+			v = make_uint4(hm.w[k / 4][4 * (k % 4)],
+			    hm.w[k / 4][4 * (k % 4) + 1], hm.w[k / 4][4 * (k % 4) + 2],
+			    hm.w[k / 4][4 * (k % 4) + 3]);
+	if (side == NET2_KT_RX && t < 16)
+		q[1 + t] = v;
+	if (side == NET2_KT_TX && t < 8)
+		q[17 + t] = v;
+	/* lane 63: the meta words, the other side's bits kept */
+	if (t == 63) {
+		uint4 mt = q[0];
+		if (side == NET2_KT_RX)
+			mt = make_uint4((mt.x & NET2_KT_TX_BITS) | bits, cutoff,
+			    rx_start, 0);
+		else if (side == NET2_KT_TX)
+			mt.x = (mt.x & NET2_KT_RX_BITS) | bits;
+		else
+			mt.x = 0;
+		q[0] = mt;
+	}
 }
 
 /* ---- coalesced small jobs (sha2_coalesce.cpp) ------------------------------- */
@@ -1700,6 +1934,34 @@ __global__ __launch_bounds__(256) void burst_prep_kernel(uint8_t *__restrict__ b
 	}
 }
 
+/* MC (the multi-connection RX burst): the cipher key is a property of the
+ * datagram's connection, so the HMAC lane marks the status of a datagram
+ * whose connection has none with BURST_NOIV, where a single-connection burst
+ * is launched with ivlen 0. */
+template <bool MC>
+__device__ __forceinline__ void burst_final_item(uint64_t i,
+    const uint8_t *__restrict__ status, const uint8_t *__restrict__ verdict,
+    const uint32_t *__restrict__ seq, const uint32_t *__restrict__ flags,
+    uint32_t ivlen, uint8_t *__restrict__ iv, uint8_t *__restrict__ result,
+    uint32_t *__restrict__ seq_out, uint32_t *__restrict__ flags_out)
+{
+	if (seq_out != nullptr) {	/* the decoded header, to the host */
+		seq_out[i] = seq[i];
+		flags_out[i] = flags[i];
+	}
+	uint32_t st = status[i];
+	const bool noiv = MC && (st & BURST_NOIV) != 0;
+	if (MC)
+		st &= ~BURST_NOIV;
+	if (st & BURST_VERIFY)		/* net2_buffer_cmp, :253-257 */
+		st = verdict[i] == 0 ? PKT_OK : PKT_BAD;
+	/* an encrypted datagram's IV from its header, :263-279 */
+	if (st == PKT_OK && !noiv && iv != nullptr && ivlen > 0 &&
+	    (flags[i] & PKT_PH_ENCRYPTED))
+		ph_iv_one(seq[i], flags[i], ivlen, iv + i * ivlen);
+	result[i] = (uint8_t)st;
+}
+
 __global__ __launch_bounds__(256) void burst_final_kernel(uint64_t n,
     const uint8_t *__restrict__ status, const uint8_t *__restrict__ verdict,
     const uint32_t *__restrict__ seq, const uint32_t *__restrict__ flags,
@@ -1709,18 +1971,20 @@ __global__ __launch_bounds__(256) void burst_final_kernel(uint64_t n,
 	const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= n)
 		return;
-	if (seq_out != nullptr) {	/* the decoded header, to the host */
-		seq_out[i] = seq[i];
-		flags_out[i] = flags[i];
-	}
-	uint32_t st = status[i];
-	if (st & BURST_VERIFY)		/* net2_buffer_cmp, :253-257 */
-		st = verdict[i] == 0 ? PKT_OK : PKT_BAD;
-	/* an encrypted datagram's IV from its header, :263-279 */
-	if (st == PKT_OK && iv != nullptr && ivlen > 0 &&
-	    (flags[i] & PKT_PH_ENCRYPTED))
-		ph_iv_one(seq[i], flags[i], ivlen, iv + i * ivlen);
-	result[i] = (uint8_t)st;
+	burst_final_item<false>(i, status, verdict, seq, flags, ivlen, iv, result,
+	    seq_out, flags_out);
+}
+
+__global__ __launch_bounds__(256) void burst_final_mc_kernel(uint64_t n,
+    const uint8_t *__restrict__ status, const uint8_t *__restrict__ verdict,
+    const uint32_t *__restrict__ seq, const uint32_t *__restrict__ flags,
+    uint32_t ivlen, uint8_t *__restrict__ iv, uint8_t *__restrict__ result)
+{
+	const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n)
+		return;
+	burst_final_item<true>(i, status, verdict, seq, flags, ivlen, iv, result,
+	    nullptr, nullptr);
 }
 
 /* ---- small bursts: a few datagrams per workgroup ------------------------- */
@@ -2882,6 +3146,83 @@ hipError_t net2_launch_hmac(int alg, const uint8_t *key, size_t keylen,
 	}
 	return hipGetLastError();
 }
+
+hipError_t net2_launch_keytab_set(int alg, Net2KeyEnt *ent, uint32_t side,
+    const uint8_t *key, const uint8_t *altkey, size_t keylen, uint32_t bits,
+    uint32_t cutoff, uint32_t rx_start, hipStream_t s)
+{
+	const int halg = alg - 3;	/* HMAC row -> SHA row */
+	if (halg < NET2_ALG_SHA256 || halg > NET2_ALG_SHA512 || ent == nullptr ||
+	    keylen > (size_t)(halg == NET2_ALG_SHA256 ? 64 : 128))
+		return hipErrorInvalidValue;
+	HMid hm = {};
+	if (side != 0) {
+		uint8_t kb[128] = { 0 };
+		if (key == nullptr)
+			return hipErrorInvalidValue;
+		for (size_t i = 0; i < keylen; i++)
+			kb[i] = key[i];
+		hmac_midstates(halg, kb, &hm, 0);
+		if (side == NET2_KT_RX && altkey != nullptr) {
+			uint8_t ab[128] = { 0 };
+			for (size_t i = 0; i < keylen; i++)
+				ab[i] = altkey[i];
+			hmac_midstates(halg, ab, &hm, 2);
+		}
+	}
+	keytab_set_kernel<<<1, 64, 0, s>>>(ent, side, bits, cutoff, rx_start, hm);
+	return hipGetLastError();
+}
+
+template <class H, bool IS384>
+static void launch_hmac_mc(int mode, unsigned grid, hipStream_t s,
+    const uint8_t *base, const uint64_t *offsets, const uint32_t *lens,
+    const uint32_t *ws, uint32_t launch, uint64_t n, uint8_t *out,
+    const KeyTabArgs &kt, const BurstArgs &rx)
+{
+	const PadKW<typename H::word> pad = {};
+	if (mode == HMAC_BURST_RX)
+		hmac_mc_kernel<H, HMAC_BURST_RX_MC, IS384><<<grid, 256, 0, s>>>(
+		    base, offsets, lens, ws, launch, n, out, kt.conn, kt.tab,
+		    kt.slots, pad, rx);
+	else
+		hmac_mc_kernel<H, HMAC_BURST_TX_MC, IS384><<<grid, 256, 0, s>>>(
+		    base, offsets, lens, ws, launch, n, out, kt.conn, kt.tab,
+		    kt.slots, pad, rx);
+}
+
+hipError_t net2_launch_hmac_mc(int alg, const KeyTabArgs &kt,
+    const uint8_t *base, const uint64_t *offsets, const uint32_t *lens,
+    uint64_t n, uint8_t *out, uint32_t *ws, hipStream_t s, int mode,
+    const BurstArgs &args)
+{
+	const int halg = alg - 3;	/* HMAC row -> SHA row */
+	if ((mode != HMAC_BURST_RX && mode != HMAC_BURST_TX) ||
+	    halg < NET2_ALG_SHA256 || halg > NET2_ALG_SHA512 ||
+	    offsets == nullptr || kt.conn == nullptr || kt.tab == nullptr ||
+	    kt.slots == 0 || args.rec != nullptr)
+		return hipErrorInvalidValue;
+	if (n == 0)
+		return hipSuccess;
+	uint32_t launch = 0;
+	if (ws != nullptr) {
+		hipError_t e = net2_bin_order(halg, lens, n, ws, s, &launch);
+		if (e != hipSuccess)
+			return e;
+	}
+	const unsigned grid = grid_for(n);
+	if (halg == NET2_ALG_SHA256)
+		launch_hmac_mc<Sha256H, false>(mode, grid, s, base, offsets, lens,
+		    ws, launch, n, out, kt, args);
+	else if (halg == NET2_ALG_SHA384)
+		launch_hmac_mc<Sha512H, true>(mode, grid, s, base, offsets, lens,
+		    ws, launch, n, out, kt, args);
+	else
+		launch_hmac_mc<Sha512H, false>(mode, grid, s, base, offsets, lens,
+		    ws, launch, n, out, kt, args);
+	return hipGetLastError();
+}
+
 template <class H, bool IS384>
 static void launch_burst_wave(int mode, uint64_t n, uint32_t G, hipStream_t s,
     const uint8_t *base, const uint64_t *offsets, const uint32_t *lens,
@@ -3038,6 +3379,19 @@ hipError_t net2_launch_burst_final(uint64_t n, const uint8_t *status,
 		return hipSuccess;
 	burst_final_kernel<<<grid_for(n), 256, 0, s>>>(n, status, verdict, seq,
 	    flags, ivlen, iv, result, seq_out, flags_out);
+	return hipGetLastError();
+}
+
+hipError_t net2_launch_burst_final_mc(uint64_t n, const uint8_t *status,
+    const uint8_t *verdict, const uint32_t *seq, const uint32_t *flags,
+    uint32_t ivlen, uint8_t *iv, uint8_t *result, hipStream_t s)
+{
+	if (ivlen > 64)
+		return hipErrorInvalidValue;
+	if (n == 0)
+		return hipSuccess;
+	burst_final_mc_kernel<<<grid_for(n), 256, 0, s>>>(n, status, verdict, seq,
+	    flags, ivlen, iv, result);
 	return hipGetLastError();
 }
 

@@ -130,6 +130,66 @@ hipError_t net2_launch_hmac(int alg, const uint8_t *key, size_t keylen,
     const BurstArgs *burst_args = nullptr);
 
 /*
+ * Device key table (net2_burst_keytab, include/net2/packet.h): one entry per
+ * connection slot, what BurstArgs + the launch's midstates hold for one
+ * connection.  400 bytes, 16-byte aligned, every midstate at a multiple of
+ * 64 bytes from the entry's start + 16, so a lane reads one with dwordx4
+ * loads:
+ *   +0    meta[0] NET2_KT_* bits, meta[1] cutoff, meta[2] rx_start, meta[3] 0
+ *   +16   rx[0] active key's K' ^ ipad midstate, rx[1] its K' ^ opad one,
+ *         rx[2..3] the same of the alternate rx key (NET2_KT_RX_ALT)
+ *   +272  tx[0..1] the tx key's ipad / opad midstates
+ * A midstate is 16 words in hmac_midstates' layout (SHA-256: 8 state words,
+ * then zeros; SHA-384/512: hi, lo of each 64-bit word).  An entry is
+ * written only by keytab_set_kernel, in stream order.
+ */
+#define NET2_KT_RX 0x01u		/* the rx side is set */
+#define NET2_KT_TX 0x02u		/* the tx side is set */
+#define NET2_KT_RX_ALT 0x04u		/* an alternate rx key is installed */
+#define NET2_KT_RX_NOCUT 0x08u		/* ... without a cutoff */
+#define NET2_KT_RX_ENC 0x10u		/* rx: a cipher key is set */
+#define NET2_KT_TX_ENC 0x20u		/* tx: a cipher key is set */
+#define NET2_KT_RX_BITS (NET2_KT_RX | NET2_KT_RX_ALT | NET2_KT_RX_NOCUT | \
+    NET2_KT_RX_ENC)
+#define NET2_KT_TX_BITS (NET2_KT_TX | NET2_KT_TX_ENC)
+struct alignas(16) Net2KeyEnt {
+	uint32_t meta[4];
+	uint32_t rx[4][16];
+	uint32_t tx[2][16];
+};
+/* The table as the multi-connection burst kernels see it: datagram i
+ * belongs to slot conn[i]; conn[i] >= slots has no connection. */
+struct KeyTabArgs {
+	const uint32_t *conn;
+	const Net2KeyEnt *tab;
+	uint32_t slots;
+};
+/*
+ * One slot's update, asynchronous on s and ordered with the bursts there:
+ * the new entry travels by value in the launch's arguments (no staging
+ * buffer to outlive the call; two updates of one slot before the first has
+ * run keep their order).  side NET2_KT_RX: key (and altkey, or NULL) are the
+ * rx keys of HMAC row alg, keylen bytes each, bits the NET2_KT_RX_* bits to
+ * set; the tx side stays.  side NET2_KT_TX: key is the tx key; the rx side
+ * stays.  side 0: both sides become unset.
+ */
+hipError_t net2_launch_keytab_set(int alg, Net2KeyEnt *ent, uint32_t side,
+    const uint8_t *key, const uint8_t *altkey, size_t keylen, uint32_t bits,
+    uint32_t cutoff, uint32_t rx_start, hipStream_t s);
+/*
+ * Keyed bursts over many connections (net2_packet_{decode,encode}_burst_mc):
+ * hmac_kernel's burst modes with the keys of datagram i taken from entry
+ * kt.conn[i] of the table.  mode NET2_HMAC_MODE_BURST_RX / _TX; args: seq,
+ * flags, status as for net2_launch_hmac (its key fields and rec are
+ * unused); status NET2_PBURST_NOCONN (5) where the slot has no such side.
+ * Always the lane form; ws as for net2_launch_var.
+ */
+hipError_t net2_launch_hmac_mc(int alg, const KeyTabArgs &kt,
+    const uint8_t *base, const uint64_t *offsets, const uint32_t *lens,
+    uint64_t n, uint8_t *out, uint32_t *ws, hipStream_t s, int mode,
+    const BurstArgs &args);
+
+/*
  * Small keyed bursts (net2_packet_{decode,encode}_burst with a hash key, at
  * most net2_burst_wave_max() datagrams): 1 to 16 datagrams per workgroup
  * (burst_wave_kernel) instead of 64 per wave -- the burst's time is one
@@ -197,6 +257,11 @@ hipError_t net2_launch_burst_final(uint64_t n, const uint8_t *status,
     const uint8_t *verdict, const uint32_t *seq, const uint32_t *flags,
     uint32_t ivlen, uint8_t *iv, uint8_t *result, hipStream_t s,
     uint32_t *seq_out = nullptr, uint32_t *flags_out = nullptr);
+/* final after net2_launch_hmac_mc's RX mode: as above, and no IV for a
+ * datagram whose connection has no cipher key (status | 0x40) */
+hipError_t net2_launch_burst_final_mc(uint64_t n, const uint8_t *status,
+    const uint8_t *verdict, const uint32_t *seq, const uint32_t *flags,
+    uint32_t ivlen, uint8_t *iv, uint8_t *result, hipStream_t s);
 
 /* Packet-header IVs (ivlen <= 64): out = n x ivlen bytes. */
 hipError_t net2_launch_ph_iv(const uint32_t *seq, const uint32_t *flags,

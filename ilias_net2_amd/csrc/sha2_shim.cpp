@@ -1963,6 +1963,219 @@ NET2_EXPORT int net2_packet_encode_burst(int hash_alg, const void *hash_key,
 	    (hipStream_t)stream, nullptr);
 }
 
+/* ---- keyed bursts over many connections: the device key table ------------- */
+
+/*
+ * The table of include/net2/packet.h: `slots` entries (Net2KeyEnt,
+ * sha2_launch.h) in the memory of the device that was current when it was
+ * made, all of one HMAC row.  Entries change only through the set / clear
+ * calls, each one launch in the caller's stream.
+ */
+struct net2_burst_keytab {
+	int device;
+	int hash_alg;
+	uint32_t slots;
+	Net2KeyEnt *ents;
+};
+
+namespace {
+
+bool hmac_row(int alg)
+{
+	return alg >= NET2_HASH_HMAC_SHA256 && alg <= NET2_HASH_HMAC_SHA512;
+}
+
+/* Arguments first (by the caller), then: a usable device, and the table's. */
+int check_keytab_device(const struct net2_burst_keytab *tab)
+{
+	int cur = -1;
+	int rc = check_current_device();
+	if (rc != 0)
+		return rc;
+	if (hipGetDevice(&cur) != hipSuccess)
+		return ENODEV;
+	return cur == tab->device ? 0 : EINVAL;
+}
+
+}	/* namespace */
+
+NET2_EXPORT int net2_burst_keytab_create(int hash_alg, uint32_t slots,
+    struct net2_burst_keytab **tab)
+{
+	if (tab == nullptr)
+		return EINVAL;
+	*tab = nullptr;
+	if (!hmac_row(hash_alg) || slots == 0)
+		return EINVAL;
+	int rc = check_current_device();
+	if (rc != 0)
+		return rc;
+	std::unique_ptr<net2_burst_keytab> t(new (std::nothrow) net2_burst_keytab());
+	if (!t)
+		return ENOMEM;
+	if (hipGetDevice(&t->device) != hipSuccess)
+		return ENODEV;
+	t->hash_alg = hash_alg;
+	t->slots = slots;
+	const size_t bytes = (size_t)slots * sizeof(Net2KeyEnt);
+	HIP_TRY(hipMalloc((void **)&t->ents, bytes));
+	/* every slot unset before the first call that could read it, whatever
+	 * stream that call uses */
+	hipError_t e = hipMemset(t->ents, 0, bytes);
+	if (e == hipSuccess)
+		e = hipDeviceSynchronize();
+	if (e != hipSuccess) {
+		(void)hipFree(t->ents);
+		return hip_fail(e);
+	}
+	*tab = t.release();
+	return 0;
+}
+
+NET2_EXPORT void net2_burst_keytab_destroy(struct net2_burst_keytab *tab)
+{
+	if (tab == nullptr)
+		return;
+	/* (hipFree waits for the work that may still read the entries) */
+	(void)hipFree(tab->ents);
+	delete tab;
+}
+
+NET2_EXPORT int net2_burst_keytab_set_rx(struct net2_burst_keytab *tab,
+    uint32_t slot, const struct net2_burst_rx_keys *keys, void *stream)
+{
+	if (tab == nullptr || keys == nullptr || slot >= tab->slots)
+		return EINVAL;
+	if (keys->hash_alg != tab->hash_alg || keys->hash_key == nullptr ||
+	    keys->hash_keylen != (size_t)kRows[tab->hash_alg].keylen)
+		return EINVAL;
+	const bool alt = keys->alt_hash_key != nullptr;
+	if (alt && keys->alt_hash_keylen != keys->hash_keylen)
+		return EINVAL;
+	int rc = check_keytab_device(tab);
+	if (rc != 0)
+		return rc;
+	const uint32_t bits = NET2_KT_RX | (keys->enc_alg != 0 ? NET2_KT_RX_ENC : 0) |
+	    (alt ? NET2_KT_RX_ALT : 0) |
+	    (alt && keys->alt_no_cutoff != 0 ? NET2_KT_RX_NOCUT : 0);
+	HIP_TRY(net2_launch_keytab_set(tab->hash_alg, tab->ents + slot, NET2_KT_RX,
+	    (const uint8_t *)keys->hash_key, (const uint8_t *)keys->alt_hash_key,
+	    keys->hash_keylen, bits, alt ? keys->alt_cutoff : 0,
+	    alt ? keys->rx_start : 0, (hipStream_t)stream));
+	return 0;
+}
+
+NET2_EXPORT int net2_burst_keytab_set_tx(struct net2_burst_keytab *tab,
+    uint32_t slot, const void *key, size_t keylen, int enc_alg, void *stream)
+{
+	if (tab == nullptr || key == nullptr || slot >= tab->slots ||
+	    keylen != (size_t)kRows[tab->hash_alg].keylen)
+		return EINVAL;
+	int rc = check_keytab_device(tab);
+	if (rc != 0)
+		return rc;
+	HIP_TRY(net2_launch_keytab_set(tab->hash_alg, tab->ents + slot, NET2_KT_TX,
+	    (const uint8_t *)key, nullptr, keylen,
+	    NET2_KT_TX | (enc_alg != 0 ? NET2_KT_TX_ENC : 0), 0, 0,
+	    (hipStream_t)stream));
+	return 0;
+}
+
+NET2_EXPORT int net2_burst_keytab_clear(struct net2_burst_keytab *tab,
+    uint32_t slot, void *stream)
+{
+	if (tab == nullptr || slot >= tab->slots)
+		return EINVAL;
+	int rc = check_keytab_device(tab);
+	if (rc != 0)
+		return rc;
+	HIP_TRY(net2_launch_keytab_set(tab->hash_alg, tab->ents + slot, 0, nullptr,
+	    nullptr, 0, 0, 0, 0, (hipStream_t)stream));
+	return 0;
+}
+
+namespace {
+
+/* What the two _mc calls share: net2_packet_*_burst's checks with a table
+ * and a connection index per datagram in place of the key. */
+int check_burst_mc_args(const struct net2_burst_keytab *tab,
+    const uint32_t *d_conn, uint32_t ivlen, const void *d_base,
+    const uint64_t *d_offsets, const uint32_t *d_lens, uint64_t n,
+    const uint8_t *d_result, const void *d_ws, size_t ws_bytes,
+    bool hdr_pair_ok)
+{
+	if (tab == nullptr || ivlen > 64)
+		return EINVAL;
+	if (n == 0)
+		return 0;
+	if (d_conn == nullptr || d_base == nullptr || d_offsets == nullptr ||
+	    d_lens == nullptr || d_result == nullptr || d_ws == nullptr ||
+	    n > UINT32_MAX || !hdr_pair_ok)
+		return EINVAL;
+	if (ws_bytes < burst_layout(n, nullptr, nullptr) ||
+	    ((uintptr_t)d_ws & 15) != 0)
+		return EINVAL;
+	return check_keytab_device(tab);
+}
+
+}	/* namespace */
+
+NET2_EXPORT int net2_packet_decode_burst_mc(const struct net2_burst_keytab *tab,
+    const uint32_t *d_conn, uint32_t ivlen, const void *d_base,
+    const uint64_t *d_offsets, const uint32_t *d_lens, uint64_t n,
+    uint8_t *d_result, void *d_iv, uint32_t *d_seq, uint32_t *d_flags,
+    void *d_ws, size_t ws_bytes, void *stream)
+{
+	int rc = check_burst_mc_args(tab, d_conn, ivlen, d_base, d_offsets,
+	    d_lens, n, d_result, d_ws, ws_bytes,
+	    (d_seq == nullptr) == (d_flags == nullptr));
+	if (rc != 0 || n == 0)
+		return rc;
+	hipStream_t s = (hipStream_t)stream;
+	BurstWs w;
+	burst_layout(n, (uint8_t *)d_ws, &w);
+	/* as decode_burst's keyed lane form: the HMAC kernel decodes the
+	 * headers to where the caller wants them (else the workspace) ... */
+	BurstArgs rx = {};
+	rx.seq = d_seq != nullptr ? d_seq : w.seq;
+	rx.flags = d_flags != nullptr ? d_flags : w.flags;
+	rx.status = w.status;
+	const KeyTabArgs kt = { d_conn, tab->ents, tab->slots };
+	HIP_TRY(net2_launch_hmac_mc(tab->hash_alg, kt, (const uint8_t *)d_base,
+	    d_offsets, d_lens, n, w.verdict, burst_bins(n, w.bin), s,
+	    NET2_HMAC_MODE_BURST_RX, rx));
+	FI_POINT(FI_KERNEL);
+	/* ... and the final kernel folds the verdicts in and derives the IV
+	 * of every OK PH_ENCRYPTED datagram whose connection has a cipher key
+	 * (one cipher, so one ivlen) */
+	HIP_TRY(net2_launch_burst_final_mc(n, w.status, w.verdict, rx.seq,
+	    rx.flags, ivlen, (uint8_t *)d_iv, d_result, s));
+	return 0;
+}
+
+NET2_EXPORT int net2_packet_encode_burst_mc(const struct net2_burst_keytab *tab,
+    const uint32_t *d_conn, const uint32_t *d_seq, const uint32_t *d_flags,
+    void *d_base, const uint64_t *d_offsets, const uint32_t *d_lens,
+    uint64_t n, uint8_t *d_result, void *d_ws, size_t ws_bytes, void *stream)
+{
+	int rc = check_burst_mc_args(tab, d_conn, 0, d_base, d_offsets, d_lens, n,
+	    d_result, d_ws, ws_bytes, d_seq != nullptr && d_flags != nullptr);
+	if (rc != 0 || n == 0)
+		return rc;
+	BurstWs w;
+	burst_layout(n, (uint8_t *)d_ws, &w);
+	BurstArgs tx = {};
+	tx.seq = const_cast<uint32_t *>(d_seq);
+	tx.flags = const_cast<uint32_t *>(d_flags);
+	tx.status = d_result;		/* the TX code is final in the kernel */
+	const KeyTabArgs kt = { d_conn, tab->ents, tab->slots };
+	HIP_TRY(net2_launch_hmac_mc(tab->hash_alg, kt, (const uint8_t *)d_base,
+	    d_offsets, d_lens, n, (uint8_t *)d_base, burst_bins(n, w.bin),
+	    (hipStream_t)stream, NET2_HMAC_MODE_BURST_TX, tx));
+	FI_POINT(FI_KERNEL);
+	return 0;
+}
+
 /* ---- packet bursts from host memory ----------------------------------------- */
 
 namespace {

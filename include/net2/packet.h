@@ -3,7 +3,8 @@
  * on the MI355X path: IV derivation from a packet header
  * (net2_ph_to_iv, packet.n2t:100-158), and the hash steps of
  * net2_packet_encode / net2_packet_decode (packet.n2t:341-463 / :170-336)
- * for whole bursts of datagrams under one connection's keys.
+ * for whole bursts of datagrams under one connection's keys or, with a
+ * device key table, under the keys of each datagram's own connection.
  */
 #ifndef NET2_PACKET_H
 #define NET2_PACKET_H
@@ -158,6 +159,92 @@ int net2_packet_encode_burst(int hash_alg, const void *hash_key,
     const uint32_t *d_flags, void *d_base, const uint64_t *d_offsets,
     const uint32_t *d_lens, uint64_t n, uint8_t *d_result, void *d_ws,
     size_t ws_bytes, void *stream);
+
+/*
+ * Keyed bursts over many connections.  The reference terminates many
+ * connections on one UDP socket (src/udp_connection.c:81-170: net2_conn_p2p
+ * keyed by remote address under one net2_udpsocket), so what a receive loop
+ * takes off the socket is the datagrams of many connections interleaved,
+ * each connection with its own negotiated key and rollover state.  A
+ * net2_burst_keytab holds that state on the device, one entry ("slot") per
+ * connection; the _mc calls below take the table and, per datagram, the slot
+ * of its connection, and hash every datagram under its own keys in one call.
+ *
+ * A table lives in the memory of the device that is current when it is
+ * created and serves one keyed hash (HMAC row 4..6); connections that
+ * negotiated another row go to another table, connections without a hash
+ * key need none (net2_packet_decode_burst with hash_alg 0).  Every slot
+ * starts with neither side set.
+ *
+ *   net2_burst_keytab_set_rx  the slot's rx side from a connection's rx key
+ *       state (keys->hash_alg must be the table's row; the alternate key,
+ *       cutoff, rx_start and enc_alg as for net2_packet_decode_burst_ck);
+ *   net2_burst_keytab_set_tx  its tx side: the key the transmitter seals
+ *       with (net2_ck_tx_key) and whether a cipher key is set;
+ *   net2_burst_keytab_clear   both sides unset (the connection is gone).
+ *
+ * Each is asynchronous on `stream` and ordered with the bursts there: a
+ * burst enqueued on the same stream before the call sees the old entry, one
+ * enqueued after it the new one -- a key commit (net2_ck_rx_key_commit,
+ * src/conn_keys.c:487-510) lands between two bursts without a host
+ * synchronisation.  The keys are consumed before the call returns (the entry
+ * travels in the launch's arguments), so they need not outlive it, and a
+ * slot set twice in a row ends with the second.  Work on other streams is
+ * not ordered with an update; the caller orders it as for any device memory.
+ * net2_burst_keytab_destroy waits for the device and frees the table.
+ *
+ * 0, EINVAL (a row that is not 4..6, keys->hash_alg not the table's, a key or
+ * alternate key of another length than the row's, slot >= slots, slots == 0,
+ * a NULL argument, or -- checked last -- a calling thread whose current
+ * device is not the table's), ENOMEM, ENODEV or EIO.
+ */
+struct net2_burst_keytab;
+int net2_burst_keytab_create(int hash_alg, uint32_t slots,
+    struct net2_burst_keytab **tab);
+void net2_burst_keytab_destroy(struct net2_burst_keytab *tab);
+int net2_burst_keytab_set_rx(struct net2_burst_keytab *tab, uint32_t slot,
+    const struct net2_burst_rx_keys *keys, void *stream);
+int net2_burst_keytab_set_tx(struct net2_burst_keytab *tab, uint32_t slot,
+    const void *key, size_t keylen, int enc_alg, void *stream);
+int net2_burst_keytab_clear(struct net2_burst_keytab *tab, uint32_t slot,
+    void *stream);
+
+/*
+ * The result code of a datagram without a connection in the _mc calls:
+ * d_conn[i] >= slots, or the slot's rx (decode) / tx (encode) side is not
+ * set.  (4 is the reference's NET2_PDECODE_WINDOW, which stays the
+ * caller's.)
+ */
+#define NET2_PBURST_NOCONN	5
+
+/*
+ * net2_packet_decode_burst_ck / net2_packet_encode_burst with the keys of
+ * datagram i taken from slot d_conn[i] of `tab` (d_conn: n uint32 in device
+ * memory).  Everything else as in those calls: the same workspace
+ * (net2_packet_burst_workspace(n)), the same outputs, asynchronous on one
+ * stream; ivlen is one per call (the reference has one cipher), and an IV
+ * is due only where the datagram's connection has a cipher key.  For
+ * identical keys the results are those of the single-connection calls, bit
+ * for bit.
+ *   RX: a datagram shorter than the header is NET2_PDECODE_BAD whatever its
+ *   connection (packet.n2t:196-198 precede the key lookup at :210);
+ *   otherwise its header is decoded (d_seq / d_flags), and without a
+ *   connection it is NET2_PBURST_NOCONN: nothing hashed, no IV written.
+ *   TX: a slot without a connection is NET2_PBURST_NOCONN and left untouched.
+ * These calls always hash one datagram per lane: net2_sha2_burst_limits'
+ * bin_min applies, wave_max does not (the one-launch small-burst form and
+ * the _host pipelines remain single-connection).
+ * EINVAL also when the calling thread's device is not the table's.
+ */
+int net2_packet_decode_burst_mc(const struct net2_burst_keytab *tab,
+    const uint32_t *d_conn, uint32_t ivlen, const void *d_base,
+    const uint64_t *d_offsets, const uint32_t *d_lens, uint64_t n,
+    uint8_t *d_result, void *d_iv, uint32_t *d_seq, uint32_t *d_flags,
+    void *d_ws, size_t ws_bytes, void *stream);
+int net2_packet_encode_burst_mc(const struct net2_burst_keytab *tab,
+    const uint32_t *d_conn, const uint32_t *d_seq, const uint32_t *d_flags,
+    void *d_base, const uint64_t *d_offsets, const uint32_t *d_lens,
+    uint64_t n, uint8_t *d_result, void *d_ws, size_t ws_bytes, void *stream);
 
 /*
  * Host-memory bursts: the same hash steps for datagrams that live in host
