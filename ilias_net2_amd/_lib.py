@@ -44,6 +44,17 @@ class BurstRxKeys(ctypes.Structure):
                 ("rx_start", ctypes.c_uint32)]
 
 
+ENC_NIL, ENC_AES256 = 0, 1     # NET2_ENC_* (include/net2/packet.h)
+
+
+class BurstCipherKeys(ctypes.Structure):
+    """struct net2_burst_cipher_keys (include/net2/packet.h)."""
+    _fields_ = [("enc_alg", ctypes.c_int), ("enc_key", ctypes.c_void_p),
+                ("enc_keylen", ctypes.c_size_t),
+                ("alt_enc_key", ctypes.c_void_p),
+                ("alt_enc_keylen", ctypes.c_size_t)]
+
+
 class BinStats(ctypes.Structure):
     """struct net2_bin_stats (include/net2/sha2_batch.h)."""
     _fields_ = [("prepared", ctypes.c_uint32), ("binned", ctypes.c_uint32),
@@ -128,6 +139,16 @@ SIGNATURES = {
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
         ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p,
         ctypes.c_size_t, ctypes.c_void_p]),
+    # the payload cipher of the bursts (AES-256-CBC)
+    "net2_packet_decrypt_burst": (ctypes.c_int, [
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p]),
+    "net2_packet_encrypt_burst": (ctypes.c_int, [
+        ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     # the device key table and the bursts over many connections
     "net2_burst_keytab_create": (ctypes.c_int, [
         ctypes.c_int, ctypes.c_uint32, ctypes.POINTER(ctypes.c_void_p)]),

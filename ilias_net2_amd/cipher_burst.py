@@ -1,0 +1,117 @@
+"""The payload cipher of the packet bursts (torch glue).
+
+``decrypt_burst`` runs after ``net2_packet_decode_burst{,_ck}`` and
+``encrypt_burst`` before ``net2_packet_encode_burst``, each on the stream of
+its hash burst: AES-256-CBC with PKCS#7 padding, the reference's ``aes256``
+(src/enc.c:70-74), over the payloads of a device-resident burst, bit for bit
+what OpenSSL's EVP computes.  PyTorch owns the memory and the streams; the
+work is the HIP kernels behind ``net2_packet_{decrypt,encrypt}_burst``
+(include/net2/packet.h).
+"""
+from __future__ import annotations
+
+import ctypes
+from typing import Optional
+
+from . import _lib
+from ._lib import check
+from .batch import _launch_stream, _need
+
+KEYLEN = 32         # AES-256
+IVLEN = 16
+
+
+def _cipher_keys(key: bytes, alt_key: Optional[bytes]):
+    """struct net2_burst_cipher_keys and the buffers it points into."""
+    kb = ctypes.create_string_buffer(bytes(key), max(len(key), 1))
+    ab = (None if alt_key is None else
+          ctypes.create_string_buffer(bytes(alt_key), max(len(alt_key), 1)))
+    ck = _lib.BurstCipherKeys(
+        _lib.ENC_AES256, ctypes.cast(kb, ctypes.c_void_p), len(key),
+        None if ab is None else ctypes.cast(ab, ctypes.c_void_p),
+        0 if alt_key is None else len(alt_key))
+    return ck, (kb, ab)
+
+
+def _burst_args(data, offsets, lens, flags, iv):
+    import torch
+    _need(data, torch.uint8, "data")
+    _need(offsets, torch.int64, "offsets")
+    _need(lens, torch.int32, "lens")
+    _need(flags, torch.int32, "flags")
+    _need(iv, torch.uint8, "iv")
+    n = int(offsets.numel())
+    if lens.numel() != n or flags.numel() != n:
+        raise ValueError("offsets, lens and flags differ in length")
+    if iv.numel() != n * IVLEN:
+        raise ValueError("iv must hold 16 bytes per datagram")
+    return n
+
+
+def decrypt_burst(hash_alg: int, key: bytes, data, offsets, lens, seq, flags,
+                  iv, result, alt_key: Optional[bytes] = None,
+                  alt_no_cutoff: bool = False, alt_cutoff: int = 0,
+                  rx_start: int = 0, out=None, stream=None):
+    """RX: decrypt the payloads of the datagrams that the hash burst left OK
+    with PH_ENCRYPTED.  ``hash_alg`` is that burst's keyed hash (0: none;
+    it sets where a signed datagram's payload starts); seq, flags (int32),
+    iv (uint8[n, 16]) and result (uint8[n]) are its outputs.  ``alt_key``:
+    the alternate key set's cipher key, when the hash burst ran with an
+    alternate key installed -- with the same cutoff arguments.  ``out``: where
+    the plaintexts go, at the datagrams' offsets (default: a new buffer;
+    ``data`` itself decrypts in place).  ``result`` is updated in place (BAD
+    for a ciphertext EVP would reject).  Returns (result, out, plen int32[n]);
+    asynchronous on ``stream`` (default: torch's current stream)."""
+    import torch
+    n = _burst_args(data, offsets, lens, flags, iv)
+    _need(seq, torch.int32, "seq")
+    _need(result, torch.uint8, "result")
+    if seq.numel() != n or result.numel() != n:
+        raise ValueError("seq and result must have one entry per datagram")
+    s = _launch_stream(stream, data.device)
+    with torch.cuda.stream(s):
+        if out is None:
+            out = torch.empty_like(data)
+        plen = torch.empty((n,), dtype=torch.int32, device=data.device)
+    _need(out, torch.uint8, "out")
+    if out.numel() < data.numel():
+        raise ValueError("out is smaller than the burst")
+    ck, keep = _cipher_keys(key, alt_key)
+    # an alternate key is installed when alt_hash_key is set; the cipher
+    # step reads only that much of the hash keys
+    rk = _lib.BurstRxKeys(hash_alg, None, 0, _lib.ENC_AES256,
+                          ck.alt_enc_key, 0, int(bool(alt_no_cutoff)),
+                          alt_cutoff & 0xffffffff, rx_start & 0xffffffff)
+    rc = _lib.lib().net2_packet_decrypt_burst(
+        ctypes.byref(rk), ctypes.byref(ck), data.data_ptr(), offsets.data_ptr(),
+        lens.data_ptr(), n, seq.data_ptr(), flags.data_ptr(), iv.data_ptr(),
+        result.data_ptr(), out.data_ptr(), plen.data_ptr(), s.cuda_stream)
+    del keep
+    check(rc, "net2_packet_decrypt_burst")
+    return result, out, plen
+
+
+def encrypt_burst(key: bytes, hashlen: int, flags, iv, data, offsets, lens,
+                  plen, stream=None):
+    """TX: slot i of ``data`` holds plen[i] (int32) plaintext bytes after the
+    header and, with PH_SIGNED, ``hashlen`` reserved bytes; with PH_ENCRYPTED
+    they are encrypted in place under iv[i] (net2_ph_to_iv_dev's output).
+    Returns (result uint8[n], wire_len int32[n]); wire_len is the ``lens`` of
+    the encode burst that follows.  Asynchronous on ``stream``."""
+    import torch
+    n = _burst_args(data, offsets, lens, flags, iv)
+    _need(plen, torch.int32, "plen")
+    if plen.numel() != n:
+        raise ValueError("plen must have one entry per datagram")
+    s = _launch_stream(stream, data.device)
+    with torch.cuda.stream(s):
+        res = torch.empty((n,), dtype=torch.uint8, device=data.device)
+        wire = torch.empty((n,), dtype=torch.int32, device=data.device)
+    ck, keep = _cipher_keys(key, None)
+    rc = _lib.lib().net2_packet_encrypt_burst(
+        ctypes.byref(ck), hashlen, flags.data_ptr(), iv.data_ptr(),
+        data.data_ptr(), offsets.data_ptr(), lens.data_ptr(), plen.data_ptr(),
+        n, res.data_ptr(), wire.data_ptr(), s.cuda_stream)
+    del keep
+    check(rc, "net2_packet_encrypt_burst")
+    return res, wire

@@ -1,0 +1,515 @@
+/*
+ * aes_kernels.hip -- the payload cipher of the packet bursts:
+ * net2_packet_decrypt_burst / net2_packet_encrypt_burst (include/net2/packet.h),
+ * the reference's "aes256" (AES-256-CBC with PKCS#7 padding, src/enc.c:70-74,
+ * :316-413) as packet.n2t applies it to a datagram's payload (:263-292 RX,
+ * :375-398 TX).
+ *
+ * One lane per datagram, as in the hash bursts: on TX the CBC chain is serial
+ * within a datagram anyway, and RX takes the same shape so both directions
+ * share the block code (aes_device.h) and the tests.
+ *
+ * LDS layout.  A workgroup is 256 lanes and holds one T-table (Te0 forward,
+ * Td0 inverse) replicated 32 times: entry x for lane l is dword
+ * x * 32 + (l & 31), 32 KiB.  A ds_read_b32 is served per half-wave of 32
+ * lanes over 32 banks, bank = dword index mod 32 = l & 31: whatever bytes
+ * the lanes look up, every lane of a half-wave reads its own bank, so no
+ * lookup conflicts and the time of a lookup does not depend on the data.
+ * The other three tables of a round are rotations of the first
+ * (v_alignbit_b32), the last round's S-box comes out of the same entries
+ * (aes_device.h).  The table is built at kernel start from the S-box with
+ * ds_write_b32 (lane t writes dwords t, t + 256, ...: consecutive banks).
+ *
+ * Round keys travel in the launch's arguments.  With one key per burst
+ * (encrypt; decrypt without an alternate rx key) they are wave-uniform and
+ * stay in scalar registers.  With an alternate rx key installed the choice
+ * is per datagram, so that instance copies both schedules to LDS (the second
+ * 272 bytes after the first: another bank) and each lane reads its own.
+ *
+ * Payloads start at 8, 40, 56 or 72 bytes past an arbitrary offset, so blocks
+ * are moved with 16-byte global accesses at byte alignment (the unaligned
+ * access mode of gfx9+ global memory that the hash kernels rely on as well).
+ * A lane touches only bytes of its own datagram's payload.
+ */
+#include "aes_device.h"
+#include "aes_launch.h"
+
+#include <string.h>
+
+namespace {
+
+constexpr uint32_t PKT_HDR = 8;			/* net2_ph_overhead */
+constexpr uint32_t PKT_PH_ENCRYPTED = 0x00000001u;
+constexpr uint32_t PKT_PH_SIGNED = 0x00000002u;
+constexpr uint32_t PKT_PH_ALTKEY = 0x80000000u;
+constexpr uint8_t PKT_OK = 0, PKT_RESOURCE = 1, PKT_BAD = 2;
+
+constexpr int AES_WG = 256;		/* lanes per workgroup = table entries */
+/* copies of the table: one per bank (-DNET2_AES_REP=1, a power of two: the
+ * plain table, for A/B runs) */
+#ifndef NET2_AES_REP
+#define NET2_AES_REP 32
+#endif
+constexpr int AES_REP = NET2_AES_REP;
+constexpr int AES_RK_STRIDE = 68;	/* words between the two LDS schedules */
+
+/* The S-box and (INV) its inverse, worked out at compile time. */
+struct Sbox {
+	uint8_t v[256];
+};
+constexpr Sbox make_sbox(bool inv)
+{
+	constexpr uint8_t s[256] = NET2_AES_SBOX_INIT;
+	Sbox r = {};
+	for (int x = 0; x < 256; x++)
+		r.v[inv ? s[x] : x] = (uint8_t)(inv ? x : s[x]);
+	return r;
+}
+constexpr Sbox h_sbox = make_sbox(false);
+__device__ const Sbox d_sbox[2] = { make_sbox(false), make_sbox(true) };
+
+struct AesSched {
+	uint32_t w[NET2_AES_RKWORDS];
+};
+template <int NK>
+struct AesKeys {
+	AesSched k[NK];
+};
+
+struct AesBurstArgs {
+	const uint8_t *in;	/* decrypt: the burst; encrypt: unused */
+	uint8_t *out;		/* decrypt: d_out; encrypt: the burst */
+	const uint64_t *offsets;
+	const uint32_t *lens;
+	const uint32_t *seq;	/* decrypt with an alternate key */
+	const uint32_t *flags;
+	const uint8_t *iv;
+	uint8_t *result;
+	uint32_t *plen;		/* decrypt: out; encrypt: in */
+	uint32_t *wire_len;	/* encrypt */
+	uint64_t n;
+	uint32_t hashlen;
+	uint32_t no_cutoff, cutoff, rx_start;
+};
+
+/* ---- host: the key schedules (FIPS 197 5.2, 5.3.5) ------------------------- */
+
+uint32_t sub_word(uint32_t w)
+{
+	return (uint32_t)h_sbox.v[w >> 24] << 24 |
+	    (uint32_t)h_sbox.v[(w >> 16) & 0xff] << 16 |
+	    (uint32_t)h_sbox.v[(w >> 8) & 0xff] << 8 | h_sbox.v[w & 0xff];
+}
+
+void aes256_enc_schedule(const uint8_t *key, AesSched *ks)
+{
+	uint32_t *w = ks->w;
+	uint32_t rcon = 1;
+	for (int i = 0; i < 8; i++)
+		w[i] = (uint32_t)key[4 * i] << 24 | (uint32_t)key[4 * i + 1] << 16 |
+		    (uint32_t)key[4 * i + 2] << 8 | key[4 * i + 3];
+	for (int i = 8; i < NET2_AES_RKWORDS; i++) {
+		uint32_t t = w[i - 1];
+		if (i % 8 == 0) {
+			t = sub_word(t << 8 | t >> 24) ^ rcon << 24;
+			rcon = aes_xtime(rcon);
+		} else if (i % 8 == 4) {
+			t = sub_word(t);
+		}
+		w[i] = w[i - 8] ^ t;
+	}
+}
+
+/* The equivalent inverse cipher's schedule: the rounds' keys in reverse
+ * order, InvMixColumns applied to all but the first and last. */
+void aes256_dec_schedule(const uint8_t *key, AesSched *ks)
+{
+	AesSched e;
+	aes256_enc_schedule(key, &e);
+	for (int r = 0; r <= NET2_AES_ROUNDS; r++) {
+		for (int c = 0; c < 4; c++) {
+			uint32_t x = e.w[4 * (NET2_AES_ROUNDS - r) + c];
+			if (r != 0 && r != NET2_AES_ROUNDS)
+				x = aes_td0_word(x >> 24) ^
+				    aes_ror(aes_td0_word((x >> 16) & 0xff), 8) ^
+				    aes_ror(aes_td0_word((x >> 8) & 0xff), 16) ^
+				    aes_ror(aes_td0_word(x & 0xff), 24);
+			ks->w[4 * r + c] = x;
+		}
+	}
+	/* the schedule is key material: leave no copy on the stack */
+	volatile uint32_t *z = e.w;
+	for (int i = 0; i < NET2_AES_RKWORDS; i++)
+		z[i] = 0;
+}
+
+/* ---- device ------------------------------------------------------------------ */
+
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+/* A block at any byte alignment <-> four big-endian words. */
+__device__ __forceinline__ void ld16(const uint8_t *p, uint32_t (&w)[4])
+{
+	u32x4 v;
+	__builtin_memcpy(&v, p, 16);
+	w[0] = __builtin_bswap32(v.x);
+	w[1] = __builtin_bswap32(v.y);
+	w[2] = __builtin_bswap32(v.z);
+	w[3] = __builtin_bswap32(v.w);
+}
+
+__device__ __forceinline__ void st16(uint8_t *p, const uint32_t (&w)[4])
+{
+	u32x4 v;
+	v.x = __builtin_bswap32(w[0]);
+	v.y = __builtin_bswap32(w[1]);
+	v.z = __builtin_bswap32(w[2]);
+	v.w = __builtin_bswap32(w[3]);
+	__builtin_memcpy(p, &v, 16);
+}
+
+/* The lane's copy of the replicated table: entry x at p[x * 32]. */
+struct LdsTab {
+	const uint32_t *p;
+	__device__ __forceinline__ uint32_t operator()(uint32_t x) const
+	{
+		return p[x * AES_REP];
+	}
+};
+
+/* Round keys out of the launch's arguments (wave-uniform) or out of LDS. */
+struct RkArgs {
+	const AesSched &k;
+	__device__ __forceinline__ uint32_t operator()(int i) const
+	{
+		return k.w[i];
+	}
+};
+struct RkLds {
+	const uint32_t *p;
+	__device__ __forceinline__ uint32_t operator()(int i) const
+	{
+		return p[i];
+	}
+};
+
+/*
+ * The workgroup's table (see the head of this file).  Every lane of the
+ * workgroup takes part; ends with a barrier.
+ */
+template <bool INV>
+__device__ __forceinline__ void aes_build_table(uint32_t *tab)
+{
+	for (uint32_t d = threadIdx.x; d < 256 * AES_REP; d += AES_WG) {
+		const uint32_t s = d_sbox[INV].v[d / AES_REP];
+		tab[d] = INV ? aes_td0_word(s) : aes_te0_word(s);
+	}
+	__syncthreads();
+}
+
+__device__ __forceinline__ uint32_t payload_at(uint32_t fl, uint32_t hashlen)
+{
+	return PKT_HDR + ((fl & PKT_PH_SIGNED) != 0 ? hashlen : 0u);
+}
+
+/*
+ * Lanes by work.  A burst mixes short and long datagrams, and a wave runs as
+ * long as its longest lane: in arrival order nearly every wave of the
+ * {64, 512, 1500}-byte mix holds a long one.  So before the cipher a
+ * workgroup ranks its 256 datagrams by block count (a counting rank over LDS,
+ * about the instructions of half a block per lane) and lane t takes the
+ * datagram of rank t: the workgroup's waves then hold datagrams of like
+ * length and the short waves retire early.  nb: the blocks of the calling
+ * lane's own datagram (0: no cipher work).  Returns the workgroup-relative
+ * index of the datagram this lane is to process and, in *nb_out, its block
+ * count.  scratch: 2 * AES_WG words of LDS, free again on return (the table
+ * is built over them); every lane of the workgroup takes part.
+ */
+__device__ __forceinline__ uint32_t lanes_by_work(uint32_t *scratch,
+    uint32_t nb, uint32_t *nb_out)
+{
+	const uint32_t t = threadIdx.x;
+	uint32_t rank = 0;
+
+	scratch[t] = nb;
+	__syncthreads();
+	for (uint32_t u = 0; u < AES_WG; u++) {
+		const uint32_t k = scratch[u];
+		rank += (k < nb || (k == nb && u < t)) ? 1u : 0u;
+	}
+	scratch[AES_WG + rank] = t;
+	__syncthreads();
+	const uint32_t me = scratch[AES_WG + t];
+	*nb_out = scratch[me];
+	__syncthreads();
+	return me;
+}
+
+/*
+ * RX.  Only a datagram that arrives OK with PH_ENCRYPTED is decrypted; every
+ * other one keeps its code, gets plen 0 and is not touched.  The last block
+ * goes first: its padding decides whether the datagram is BAD (as is an empty
+ * or ragged ciphertext), and a BAD datagram is not written at all.  Then the
+ * blocks in order, the next one's ciphertext loaded before the current one is
+ * decrypted; in place, a block is overwritten only after it and its
+ * predecessor's ciphertext are in registers.
+ */
+
+/* Datagram i's ciphertext blocks; what needs no cipher is settled here. */
+__device__ __forceinline__ uint32_t decrypt_prep(const AesBurstArgs &a,
+    uint64_t i)
+{
+	if (i >= a.n)
+		return 0;
+	const uint32_t fl = a.flags[i];
+	uint32_t nb = 0;
+	if (a.result[i] == PKT_OK && (fl & PKT_PH_ENCRYPTED) != 0) {
+		const uint32_t po = payload_at(fl, a.hashlen);
+		const uint32_t len = a.lens[i];
+		const uint32_t clen = len > po ? len - po : 0u;
+		if (clen != 0 && (clen & 15u) == 0)
+			nb = clen >> 4;
+		else
+			a.result[i] = PKT_BAD;
+	}
+	if (nb == 0)
+		a.plen[i] = 0;
+	return nb;
+}
+
+template <bool ALT>
+__global__ __launch_bounds__(AES_WG) void aes_cbc_decrypt_kernel(
+    const AesBurstArgs a, const AesKeys<ALT ? 2 : 1> keys)
+{
+	__shared__ uint32_t tab[256 * AES_REP > 2 * AES_WG ? 256 * AES_REP :
+	    2 * AES_WG];
+	__shared__ __attribute__((aligned(16))) uint32_t
+	    rks[ALT ? 2 * AES_RK_STRIDE : 4];
+
+	if (ALT) {
+		const uint32_t t = threadIdx.x;
+		if (t < NET2_AES_RKWORDS)
+			rks[t] = keys.k[0].w[t];
+		else if (t >= 64 && t < 64 + NET2_AES_RKWORDS)
+			rks[AES_RK_STRIDE + t - 64] = keys.k[ALT ? 1 : 0].w[t - 64];
+	}
+	const uint64_t first = (uint64_t)blockIdx.x * AES_WG;
+	uint32_t nb;
+	const uint64_t i = first + lanes_by_work(tab,
+	    decrypt_prep(a, first + threadIdx.x), &nb);
+	aes_build_table<true>(tab);
+	if (nb == 0)
+		return;
+
+	const uint32_t fl = a.flags[i];
+	const uint32_t po = payload_at(fl, a.hashlen);
+	const LdsTab T = { tab + (threadIdx.x & (AES_REP - 1)) };
+	/* net2_ck_rx_key (src/conn_keys.c:447-476), as the HMAC step chose */
+	const bool alt = ALT && ((fl & PKT_PH_ALTKEY) != 0 || (a.no_cutoff == 0 &&
+	    a.seq[i] - a.rx_start >= a.cutoff - a.rx_start));
+	const RkLds KL = { rks + (alt ? AES_RK_STRIDE : 0) };
+	const RkArgs KA = { keys.k[0] };
+	const uint64_t off = a.offsets[i] + po;
+	const uint8_t *src = a.in + off;
+	uint8_t *dst = a.out + off;
+	uint32_t ivw[4], c[4], prev[4];
+	uint32_t b = nb - 1, pad = 0;
+
+	ld16(a.iv + NET2_AES_BLOCK * i, ivw);
+	ld16(src + 16 * (uint64_t)b, c);
+	if (nb > 1) {
+		ld16(src + 16 * (uint64_t)(b - 1), prev);
+	} else {
+#pragma unroll
+		for (int k = 0; k < 4; k++)
+			prev[k] = ivw[k];
+	}
+	for (uint32_t j = 0; j < nb; j++) {
+		const uint32_t bn = j == 0 ? 0u : b + 1;
+		uint32_t cn[4] = { 0, 0, 0, 0 };
+		if (j + 1 < nb)
+			ld16(src + 16 * (uint64_t)bn, cn);
+		uint32_t x[4] = { c[0], c[1], c[2], c[3] };
+		if (ALT)
+			aes_block<true>(T, KL, x);
+		else
+			aes_block<true>(T, KA, x);
+#pragma unroll
+		for (int k = 0; k < 4; k++)
+			x[k] ^= prev[k];
+		if (j == 0) {
+			pad = aes_pkcs7_pad(x);
+			if (pad == 0)
+				break;
+		}
+		st16(dst + 16 * (uint64_t)b, x);
+#pragma unroll
+		for (int k = 0; k < 4; k++) {
+			prev[k] = j == 0 ? ivw[k] : c[k];
+			c[k] = cn[k];
+		}
+		b = bn;
+	}
+	if (pad == 0)
+		a.result[i] = PKT_BAD;
+	a.plen[i] = pad != 0 ? 16 * nb - pad : 0u;
+}
+
+/*
+ * TX.  Slot i holds plen[i] plaintext bytes at its payload offset.  With
+ * PH_ENCRYPTED they are encrypted in place into 16 * (plen / 16 + 1) bytes
+ * (EVP always pads); a slot without the room is RESOURCE and untouched.
+ * The next block's plaintext is loaded before the current one goes through
+ * the chain; the last, partial block is read bytewise and padded.
+ */
+
+/* Slot i's blocks to encrypt; what needs no cipher is settled here. */
+__device__ __forceinline__ uint32_t encrypt_prep(const AesBurstArgs &a,
+    uint64_t i)
+{
+	if (i >= a.n)
+		return 0;
+	const uint32_t fl = a.flags[i];
+	const uint32_t pl = a.plen[i];
+	const uint32_t len = a.lens[i];
+	const uint32_t po = payload_at(fl, a.hashlen);
+	if ((fl & PKT_PH_ENCRYPTED) == 0) {
+		const uint64_t wl = (uint64_t)po + pl;
+		a.wire_len[i] = (uint32_t)wl;
+		a.result[i] = wl > len ? PKT_RESOURCE : PKT_OK;
+		return 0;
+	}
+	const uint64_t clen = 16 * ((uint64_t)pl / 16 + 1);
+	const bool room = po + clen <= len;
+	a.wire_len[i] = room ? po + (uint32_t)clen : 0u;
+	a.result[i] = room ? PKT_OK : PKT_RESOURCE;
+	return room ? (uint32_t)(clen >> 4) : 0u;
+}
+
+__global__ __launch_bounds__(AES_WG) void aes_cbc_encrypt_kernel(
+    const AesBurstArgs a, const AesKeys<1> keys)
+{
+	__shared__ uint32_t tab[256 * AES_REP > 2 * AES_WG ? 256 * AES_REP :
+	    2 * AES_WG];
+
+	const uint64_t first = (uint64_t)blockIdx.x * AES_WG;
+	uint32_t nb;
+	const uint64_t i = first + lanes_by_work(tab,
+	    encrypt_prep(a, first + threadIdx.x), &nb);
+	aes_build_table<false>(tab);
+	if (nb == 0)
+		return;
+
+	const LdsTab T = { tab + (threadIdx.x & (AES_REP - 1)) };
+	const RkArgs K = { keys.k[0] };
+	uint8_t *p = a.out + a.offsets[i] + payload_at(a.flags[i], a.hashlen);
+	const uint32_t rem = a.plen[i] & 15u;
+	uint32_t chain[4], cur[4];
+
+	/* block j of the padded plaintext: whole, or the tail and its padding */
+	auto load = [&](uint32_t j, uint32_t (&w)[4]) {
+		const uint8_t *q = p + 16 * (uint64_t)j;
+		if (j + 1 < nb) {
+			ld16(q, w);
+			return;
+		}
+		w[0] = w[1] = w[2] = w[3] = 0;
+#pragma unroll
+		for (uint32_t k = 0; k < 16; k++) {
+			const uint32_t v = k < rem ? q[k] : 16u - rem;
+			w[k / 4] |= v << (24 - 8 * (k % 4));
+		}
+	};
+
+	ld16(a.iv + NET2_AES_BLOCK * i, chain);
+	load(0, cur);
+	for (uint32_t j = 0; j < nb; j++) {
+		uint32_t nx[4] = { 0, 0, 0, 0 };
+		if (j + 1 < nb)
+			load(j + 1, nx);
+#pragma unroll
+		for (int k = 0; k < 4; k++)
+			chain[k] ^= cur[k];
+		aes_block<false>(T, K, chain);
+		st16(p + 16 * (uint64_t)j, chain);
+#pragma unroll
+		for (int k = 0; k < 4; k++)
+			cur[k] = nx[k];
+	}
+}
+
+void wipe(void *p, size_t n)
+{
+	volatile uint8_t *z = (volatile uint8_t *)p;
+	while (n-- > 0)
+		*z++ = 0;
+}
+
+}	/* namespace */
+
+hipError_t net2_launch_aes_decrypt(const uint8_t *key, const AesRxAlt &alt,
+    uint32_t hashlen, const uint8_t *base, const uint64_t *offsets,
+    const uint32_t *lens, uint64_t n, const uint32_t *seq,
+    const uint32_t *flags, const uint8_t *iv, uint8_t *result, uint8_t *out,
+    uint32_t *plen, hipStream_t s)
+{
+	if (n == 0)
+		return hipSuccess;
+	AesBurstArgs a = {};
+	a.in = base;
+	a.out = out;
+	a.offsets = offsets;
+	a.lens = lens;
+	a.seq = seq;
+	a.flags = flags;
+	a.iv = iv;
+	a.result = result;
+	a.plen = plen;
+	a.n = n;
+	a.hashlen = hashlen;
+	a.no_cutoff = alt.no_cutoff != 0;
+	a.cutoff = alt.cutoff;
+	a.rx_start = alt.rx_start;
+	const dim3 grid((unsigned)((n + AES_WG - 1) / AES_WG));
+	if (alt.alt_key != nullptr) {
+		AesKeys<2> k;
+		aes256_dec_schedule(key, &k.k[0]);
+		aes256_dec_schedule(alt.alt_key, &k.k[1]);
+		hipLaunchKernelGGL(aes_cbc_decrypt_kernel<true>, grid, dim3(AES_WG),
+		    0, s, a, k);
+		wipe(&k, sizeof(k));
+	} else {
+		AesKeys<1> k;
+		aes256_dec_schedule(key, &k.k[0]);
+		hipLaunchKernelGGL(aes_cbc_decrypt_kernel<false>, grid, dim3(AES_WG),
+		    0, s, a, k);
+		wipe(&k, sizeof(k));
+	}
+	return hipGetLastError();
+}
+
+hipError_t net2_launch_aes_encrypt(const uint8_t *key, uint32_t hashlen,
+    const uint32_t *flags, const uint8_t *iv, uint8_t *base,
+    const uint64_t *offsets, const uint32_t *lens, const uint32_t *plen,
+    uint64_t n, uint8_t *result, uint32_t *wire_len, hipStream_t s)
+{
+	if (n == 0)
+		return hipSuccess;
+	AesBurstArgs a = {};
+	a.out = base;
+	a.offsets = offsets;
+	a.lens = lens;
+	a.flags = flags;
+	a.iv = iv;
+	a.result = result;
+	a.plen = const_cast<uint32_t *>(plen);
+	a.wire_len = wire_len;
+	a.n = n;
+	a.hashlen = hashlen;
+	AesKeys<1> k;
+	aes256_enc_schedule(key, &k.k[0]);
+	hipLaunchKernelGGL(aes_cbc_encrypt_kernel,
+	    dim3((unsigned)((n + AES_WG - 1) / AES_WG)), dim3(AES_WG), 0, s, a, k);
+	wipe(&k, sizeof(k));
+	return hipGetLastError();
+}

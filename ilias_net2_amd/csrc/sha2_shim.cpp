@@ -12,6 +12,7 @@
  */
 #include "sha2_launch.h"
 #include "sha2_coalesce.h"
+#include "aes_launch.h"
 
 #include <hip/hip_runtime.h>
 
@@ -1961,6 +1962,85 @@ NET2_EXPORT int net2_packet_encode_burst(int hash_alg, const void *hash_key,
 	return encode_burst(hash_alg, hash_key, hash_keylen, enc_alg, d_seq,
 	    d_flags, d_base, d_offsets, d_lens, n, d_result, d_ws,
 	    (hipStream_t)stream, nullptr);
+}
+
+/* ---- the payload cipher of the bursts (aes_kernels.hip) -------------------- */
+
+namespace {
+
+/* aes256 with a 32-byte key, and as long an alternate key or none */
+int check_cipher_keys(const struct net2_burst_cipher_keys *ck)
+{
+	if (ck == nullptr || ck->enc_alg != NET2_ENC_AES256)
+		return EINVAL;
+	if (ck->enc_key == nullptr || ck->enc_keylen != NET2_AES_KEYLEN)
+		return EINVAL;
+	if (ck->alt_enc_key != nullptr && ck->alt_enc_keylen != NET2_AES_KEYLEN)
+		return EINVAL;
+	return 0;
+}
+
+}	/* namespace */
+
+NET2_EXPORT int net2_packet_decrypt_burst(const struct net2_burst_rx_keys *k,
+    const struct net2_burst_cipher_keys *ck, const void *d_base,
+    const uint64_t *d_offsets, const uint32_t *d_lens, uint64_t n,
+    const uint32_t *d_seq, const uint32_t *d_flags, const void *d_iv,
+    uint8_t *d_result, void *d_out, uint32_t *d_plen, void *stream)
+{
+	if (k == nullptr || check_cipher_keys(ck) != 0)
+		return EINVAL;
+	if (k->hash_alg != NET2_HASH_NIL && (k->hash_alg < NET2_HASH_HMAC_SHA256 ||
+	    k->hash_alg > NET2_HASH_HMAC_SHA512))
+		return EINVAL;
+	/* the alternate cipher key goes with the alternate hash key: the HMAC
+	 * step's choice of key set is the one made here */
+	const bool alt = k->alt_hash_key != nullptr;
+	if (alt && (k->hash_alg == NET2_HASH_NIL || ck->alt_enc_key == nullptr))
+		return EINVAL;
+	if (n == 0)
+		return 0;
+	if (d_base == nullptr || d_offsets == nullptr || d_lens == nullptr ||
+	    d_flags == nullptr || d_iv == nullptr || d_result == nullptr ||
+	    d_out == nullptr || d_plen == nullptr || (alt && d_seq == nullptr) ||
+	    n > UINT32_MAX)
+		return EINVAL;
+	int rc = check_current_device();
+	if (rc != 0)
+		return rc;
+	const AesRxAlt ra = { alt ? (const uint8_t *)ck->alt_enc_key : nullptr,
+	    k->alt_no_cutoff, k->alt_cutoff, k->rx_start };
+	HIP_TRY(net2_launch_aes_decrypt((const uint8_t *)ck->enc_key, ra,
+	    k->hash_alg != NET2_HASH_NIL ? (uint32_t)digest_len(k->hash_alg) : 0,
+	    (const uint8_t *)d_base, d_offsets, d_lens, n, d_seq, d_flags,
+	    (const uint8_t *)d_iv, d_result, (uint8_t *)d_out, d_plen,
+	    (hipStream_t)stream));
+	return 0;
+}
+
+NET2_EXPORT int net2_packet_encrypt_burst(
+    const struct net2_burst_cipher_keys *ck, uint32_t hashlen,
+    const uint32_t *d_flags, const void *d_iv, void *d_base,
+    const uint64_t *d_offsets, const uint32_t *d_lens, const uint32_t *d_plen,
+    uint64_t n, uint8_t *d_result, uint32_t *d_wire_len, void *stream)
+{
+	if (check_cipher_keys(ck) != 0)
+		return EINVAL;
+	if (hashlen != 0 && hashlen != 32 && hashlen != 48 && hashlen != 64)
+		return EINVAL;
+	if (n == 0)
+		return 0;
+	if (d_flags == nullptr || d_iv == nullptr || d_base == nullptr ||
+	    d_offsets == nullptr || d_lens == nullptr || d_plen == nullptr ||
+	    d_result == nullptr || d_wire_len == nullptr || n > UINT32_MAX)
+		return EINVAL;
+	int rc = check_current_device();
+	if (rc != 0)
+		return rc;
+	HIP_TRY(net2_launch_aes_encrypt((const uint8_t *)ck->enc_key, hashlen,
+	    d_flags, (const uint8_t *)d_iv, (uint8_t *)d_base, d_offsets, d_lens,
+	    d_plen, n, d_result, d_wire_len, (hipStream_t)stream));
+	return 0;
 }
 
 /* ---- keyed bursts over many connections: the device key table ------------- */

@@ -98,8 +98,9 @@ int net2_sha2_burst_limits(int64_t wave_max, int64_t bin_min);
  *   - PH_ENCRYPTED and OK: the IV for the decryption step,
  *     net2_ph_to_iv (:263-279), to d_iv + i * ivlen (d_iv may be NULL).
  * d_result[i] receives the code; d_seq / d_flags (both or neither) the
- * decoded header.  The window check, the decryption itself and the key
- * commit (:200-206, :283-313) stay with the caller.
+ * decoded header.  The decryption itself (:283-292) is
+ * net2_packet_decrypt_burst below; the window check and the key commit
+ * (:200-206, :293-313) stay with the caller.
  */
 int net2_packet_decode_burst(int hash_alg, const void *hash_key,
     size_t hash_keylen, int enc_alg, uint32_t ivlen, const void *d_base,
@@ -145,7 +146,8 @@ int net2_packet_decode_burst_ck(const struct net2_burst_rx_keys *keys,
  * d_base[d_offsets[i] .. + d_lens[i]) holds, on entry, 8 bytes for the
  * header, then hashlen reserved bytes when d_flags[i] has PH_SIGNED (as
  * connection.c:336-339 reserves them), then the payload -- already
- * encrypted when PH_ENCRYPTED (its IV comes from net2_ph_to_iv_dev first).
+ * encrypted when PH_ENCRYPTED (its IV comes from net2_ph_to_iv_dev first,
+ * the encryption from net2_packet_encrypt_burst below).
  * The flags are checked against the keys both ways (NET2_PENCODE_UNSAFE,
  * :364-370); then the header (d_seq[i], d_flags[i]) is written big-endian
  * and, when PH_SIGNED, the HMAC of the payload into the reserved field
@@ -159,6 +161,81 @@ int net2_packet_encode_burst(int hash_alg, const void *hash_key,
     const uint32_t *d_flags, void *d_base, const uint64_t *d_offsets,
     const uint32_t *d_lens, uint64_t n, uint8_t *d_result, void *d_ws,
     size_t ws_bytes, void *stream);
+
+/*
+ * The payload cipher of a burst: the decryption step of net2_packet_decode
+ * (packet.n2t:263-292) after net2_packet_decode_burst{,_ck}, and the
+ * encryption step of net2_packet_encode (:375-398) before
+ * net2_packet_encode_burst, each on the same stream as its hash burst,
+ * device-resident and asynchronous (no host synchronisation).  The cipher is
+ * the reference's one real cipher, aes256 (src/enc.c:70-74): AES-256-CBC as
+ * OpenSSL's EVP runs it, PKCS#7 padding included (:316-413), bit for bit.
+ *
+ * The payload of datagram i starts po(i) = 8 + (flags[i] & PH_SIGNED ?
+ * hashlen : 0) bytes into the datagram, at any alignment; its IV is the 16
+ * bytes at d_iv + 16 * i, as the decode burst and net2_ph_to_iv_dev write
+ * them with ivlen 16.  The round keys are expanded on the host inside the
+ * call and travel in the launch's arguments, so the keys need not outlive it.
+ *
+ * Both return 0, EINVAL (enc_alg not NET2_ENC_AES256, a key or alternate key
+ * that is not 32 bytes, hashlen not 0, 32, 48 or 64, a NULL pointer while
+ * n > 0, or the alternate-key mismatches below -- all checked before the
+ * device), ENOMEM, ENODEV or EIO; n == 0 is 0 and launches nothing.
+ */
+#define NET2_ENC_NIL		0
+#define NET2_ENC_AES256		1	/* src/enc.c:70-74 */
+struct net2_burst_cipher_keys {
+	int enc_alg;			/* NET2_ENC_AES256 */
+	const void *enc_key;		/* the active key, 32 bytes */
+	size_t enc_keylen;
+	const void *alt_enc_key;	/* NULL: no alternate key */
+	size_t alt_enc_keylen;		/* 0 or 32 */
+};
+
+/*
+ * RX.  keys: the rx key state the hash burst ran under (hashlen is the digest
+ * length of keys->hash_alg, 0 without one); d_seq, d_flags, d_iv, d_result:
+ * that burst's outputs.  Only a datagram with d_result[i] == NET2_PDECODE_OK
+ * and PH_ENCRYPTED is decrypted; every other one keeps its code, gets
+ * d_plen[i] = 0, and nothing of it is written.  A key set carries both keys:
+ * datagram i takes ck->alt_enc_key exactly where the hash step took the
+ * alternate hash key (net2_ck_rx_key, src/conn_keys.c:447-476, over
+ * keys->alt_*, rx_start, d_seq[i], d_flags[i]); an alternate key is installed
+ * when keys->alt_hash_key != NULL, and then ck->alt_enc_key must be set, d_seq
+ * must be given and keys->hash_alg must not be 0 (EINVAL otherwise).
+ * The ciphertext is the d_lens[i] - po(i) bytes of the payload.  Empty, not a
+ * multiple of 16, or with a last block that fails EVP's padding check (the
+ * last byte v in 1..16, the last v bytes all v): d_result[i] =
+ * NET2_PDECODE_BAD, d_plen[i] = 0 (net2_encctx_encbuf returning NULL,
+ * :288-291), and nothing of the datagram is written.  Otherwise the plaintext
+ * goes to d_out + d_offsets[i] + po(i) and its length to d_plen[i]; what
+ * follows it within the datagram's own bytes of d_out is unspecified.  No
+ * byte outside a decrypted datagram's payload is written.  d_out == d_base
+ * decrypts in place; any other d_out must not overlap the burst.
+ */
+int net2_packet_decrypt_burst(const struct net2_burst_rx_keys *keys,
+    const struct net2_burst_cipher_keys *ck, const void *d_base,
+    const uint64_t *d_offsets, const uint32_t *d_lens, uint64_t n,
+    const uint32_t *d_seq, const uint32_t *d_flags, const void *d_iv,
+    uint8_t *d_result, void *d_out, uint32_t *d_plen, void *stream);
+
+/*
+ * TX.  Slot i holds d_plen[i] plaintext bytes at po(i).  Without
+ * PH_ENCRYPTED it is left as it is: d_wire_len[i] = po + plen, the code
+ * NET2_PENCODE_OK, or NET2_PENCODE_RESOURCE when that exceeds d_lens[i].
+ * With PH_ENCRYPTED the payload becomes clen = 16 * (plen / 16 + 1) bytes
+ * (EVP always pads: an empty plaintext is one block): when po + clen >
+ * d_lens[i] the code is NET2_PENCODE_RESOURCE, the slot untouched and
+ * d_wire_len[i] = 0; otherwise it is encrypted in place and d_wire_len[i] =
+ * po + clen.  d_wire_len is what net2_packet_encode_burst takes as d_lens;
+ * the checks of the flags against the keys stay there.  ck's alternate key is
+ * not used (the transmitter picks the key set before it builds a datagram).
+ */
+int net2_packet_encrypt_burst(const struct net2_burst_cipher_keys *ck,
+    uint32_t hashlen, const uint32_t *d_flags, const void *d_iv,
+    void *d_base, const uint64_t *d_offsets, const uint32_t *d_lens,
+    const uint32_t *d_plen, uint64_t n, uint8_t *d_result,
+    uint32_t *d_wire_len, void *stream);
 
 /*
  * Keyed bursts over many connections.  The reference terminates many
