@@ -1,5 +1,5 @@
 /*
- * aes_launch.h -- internal interface between the C-ABI shim (sha2_shim.cpp)
+ * aes_launch.h -- internal interface between the host units (net2_dgram.cpp)
  * and the burst cipher kernels (aes_kernels.hip).  Not installed; the public
  * surface is net2_packet_{decrypt,encrypt}_burst in include/net2/packet.h.
  */

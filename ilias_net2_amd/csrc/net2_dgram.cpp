@@ -1,0 +1,651 @@
+/*
+ * net2_dgram.cpp -- the calls on device-resident datagrams: HMAC sign /
+ * verify and header IVs, the packet bursts, the payload cipher, the key table
+ * and the bursts over many connections (include/net2/packet.h).  Argument
+ * checks and launches in the caller's stream; nothing is staged here.
+ */
+#include "net2_host.h"
+#include "aes_launch.h"
+
+#include <atomic>
+#include <new>
+
+/* Argument checks shared by the datagram sign / verify entry points. */
+static int check_dgram_args(int alg, const void *key, size_t keylen,
+    const void *d_base, const uint64_t *d_offsets, const uint32_t *d_lens,
+    uint64_t n, const void *d_ws, size_t ws_bytes)
+{
+	if (!hmac_key_ok(alg, key, keylen, false))
+		return EINVAL;
+	if (n == 0)
+		return 0;
+	/* (without a workspace, no limit on n: nothing is indexed by it) */
+	if (d_base == nullptr || d_offsets == nullptr || d_lens == nullptr ||
+	    !bin_ws_ok(d_ws, ws_bytes, n))
+		return EINVAL;
+	return check_current_device();
+}
+
+NET2_EXPORT int net2_hmac_sign_dev(int alg, const void *key, size_t keylen,
+    void *d_base, const uint64_t *d_offsets, const uint32_t *d_lens,
+    uint64_t n, void *d_ws, size_t ws_bytes, void *stream)
+{
+	int rc = check_dgram_args(alg, key, keylen, d_base, d_offsets, d_lens,
+	    n, d_ws, ws_bytes);
+	if (rc != 0 || n == 0)
+		return rc;
+	HIP_TRY(net2_launch_hmac(alg, (const uint8_t *)key, keylen,
+	    (const uint8_t *)d_base, d_offsets, d_lens, 0, 0, n,
+	    (uint8_t *)d_base, (uint32_t *)d_ws, (hipStream_t)stream,
+	    NET2_HMAC_MODE_SIGN));
+	return 0;
+}
+
+NET2_EXPORT int net2_hmac_verify_dev(int alg, const void *key,
+    size_t keylen, const void *d_base, const uint64_t *d_offsets,
+    const uint32_t *d_lens, uint64_t n, uint8_t *d_result, void *d_ws,
+    size_t ws_bytes, void *stream)
+{
+	int rc = check_dgram_args(alg, key, keylen, d_base, d_offsets, d_lens,
+	    n, d_ws, ws_bytes);
+	if (rc != 0 || n == 0)
+		return rc;
+	if (d_result == nullptr)
+		return EINVAL;
+	HIP_TRY(net2_launch_hmac(alg, (const uint8_t *)key, keylen,
+	    (const uint8_t *)d_base, d_offsets, d_lens, 0, 0, n, d_result,
+	    (uint32_t *)d_ws, (hipStream_t)stream, NET2_HMAC_MODE_VERIFY));
+	return 0;
+}
+
+NET2_EXPORT int net2_hmac_dev(int alg, const void *key, size_t keylen,
+    const void *d_base, const uint64_t *d_offsets, const uint32_t *d_lens,
+    uint64_t stride, uint32_t fixed_len, uint64_t n, void *d_digests,
+    void *d_ws, size_t ws_bytes, void *stream)
+{
+	if (!hmac_key_ok(alg, key, keylen, false))
+		return EINVAL;
+	if (n == 0)
+		return 0;
+	if (d_digests == nullptr)
+		return EINVAL;
+	if (d_offsets != nullptr) {
+		if (d_lens == nullptr || !bin_ws_ok(d_ws, ws_bytes, n))
+			return EINVAL;
+	} else {
+		if (d_base == nullptr && fixed_len > 0)
+			return EINVAL;
+		if (n > 1 && stride < fixed_len)
+			return EINVAL;
+	}
+	if (int rc = check_current_device())
+		return rc;
+	HIP_TRY(net2_launch_hmac(alg, (const uint8_t *)key, keylen,
+	    (const uint8_t *)d_base, d_offsets, d_lens, stride, fixed_len, n,
+	    (uint8_t *)d_digests, d_offsets ? (uint32_t *)d_ws : nullptr,
+	    (hipStream_t)stream));
+	return 0;
+}
+
+NET2_EXPORT int net2_ph_to_iv_dev(const uint32_t *d_seq,
+    const uint32_t *d_flags, uint64_t n, uint32_t ivlen, void *d_iv,
+    void *stream)
+{
+	if (n == 0 || ivlen == 0)
+		return 0;
+	if (ivlen > 64 || d_seq == nullptr || d_flags == nullptr ||
+	    d_iv == nullptr)
+		return EINVAL;
+	if (int rc = check_current_device())
+		return rc;
+	HIP_TRY(net2_launch_ph_iv(d_seq, d_flags, n, ivlen, (uint8_t *)d_iv,
+	    (hipStream_t)stream));
+	return 0;
+}
+
+/* ---- packet bursts (include/net2/packet.h) --------------------------------- */
+
+/* Workspace of a burst, carved in this order, every piece 16-byte aligned:
+ * the binning scratch first -- its header and histograms at offset 0 for
+ * every n, so one workspace serves bursts of any size up to its own and
+ * net2_sha2_workspace_init / _stats apply to it -- then region offsets and
+ * lengths for the prep kernel, status and verdict bytes, decoded headers. */
+struct BurstWs {
+	uint64_t *sub_off;
+	uint32_t *sub_len;
+	uint8_t *status, *verdict;
+	uint32_t *seq, *flags;
+	uint32_t *bin;
+};
+
+size_t burst_layout(uint64_t n, uint8_t *base, BurstWs *w)
+{
+	size_t at = 0;
+	auto take = [&](size_t bytes) {
+		uint8_t *p = base ? base + at : nullptr;
+		at += a16(bytes);
+		return p;
+	};
+	uint32_t *bn = (uint32_t *)take(((size_t)NET2_BIN_WS_WORDS + n) * 4);
+	uint64_t *so = (uint64_t *)take(8 * n);
+	uint32_t *sl = (uint32_t *)take(4 * n);
+	uint8_t *st = take(n);
+	uint8_t *vd = take(n);
+	uint32_t *sq = (uint32_t *)take(4 * n);
+	uint32_t *fl = (uint32_t *)take(4 * n);
+	if (w != nullptr)
+		*w = { so, sl, st, vd, sq, fl, bn };
+	return at;
+}
+
+namespace {
+
+/* A workspace of an n-datagram burst (n <= UINT32_MAX): there, as large as
+ * the layout and 16-byte aligned. */
+bool burst_ws_ok(const void *d_ws, size_t ws_bytes, uint64_t n)
+{
+	return d_ws != nullptr && ws_bytes >= burst_layout(n, nullptr, nullptr) &&
+	    ((uintptr_t)d_ws & 15) == 0;
+}
+
+/* hash_alg 0 (none) or an HMAC row with its key; ivlen <= 64 */
+int check_burst_args(int hash_alg, const void *key, size_t keylen,
+    uint32_t ivlen, const void *d_base, const uint64_t *d_offsets,
+    const uint32_t *d_lens, uint64_t n, const uint8_t *d_result,
+    const void *d_ws, size_t ws_bytes)
+{
+	if (!hmac_key_ok(hash_alg, key, keylen, true))
+		return EINVAL;
+	int rc = check_burst_arrays(ivlen, d_base, d_offsets, d_lens, n, d_result);
+	if (rc != 0 || n == 0)
+		return rc;
+	return burst_ws_ok(d_ws, ws_bytes, n) ? check_current_device() : EINVAL;
+}
+
+/* the cipher calls: aes256 with a 32-byte key, and as long an alternate key
+ * or none */
+int check_cipher_keys(const struct net2_burst_cipher_keys *ck)
+{
+	if (ck == nullptr || ck->enc_alg != NET2_ENC_AES256)
+		return EINVAL;
+	if (ck->enc_key == nullptr || ck->enc_keylen != NET2_AES_KEYLEN)
+		return EINVAL;
+	if (ck->alt_enc_key != nullptr && ck->alt_enc_keylen != NET2_AES_KEYLEN)
+		return EINVAL;
+	return 0;
+}
+
+/* net2_sha2_burst_limits' binning threshold (-1: none) */
+std::atomic<int64_t> g_burst_bin_min{-1};
+
+/*
+ * The binning workspace a burst's HMAC kernel is given: below the binning
+ * threshold (default 65,536 datagrams: one lane per datagram, one wave per
+ * SIMD) none -- every wave then has a SIMD of its own, the burst takes its
+ * longest wave's time whatever the order, and the binning launch is pure
+ * fixed cost (tools/burst_sizes.py).  The threshold is
+ * net2_sha2_burst_limits' setting, else NET2_BURST_BIN_MIN from the
+ * environment at first use (A/B runs), else the default.
+ */
+uint32_t *burst_bins(uint64_t n, uint32_t *bin)
+{
+	int64_t min_n = g_burst_bin_min.load(std::memory_order_relaxed);
+	if (min_n < 0) {
+		static const int64_t env = [] {
+			const char *e = getenv("NET2_BURST_BIN_MIN");
+			return e != nullptr && *e != '\0' ?
+			    (int64_t)(strtoull(e, nullptr, 10) & INT64_MAX) :
+			    (int64_t)65536;
+		}();
+		min_n = env;
+	}
+	return n >= (uint64_t)min_n ? bin : nullptr;
+}
+
+}	/* namespace */
+
+/*
+ * The hash steps of net2_packet_decode for a device-resident burst.
+ * hdr_out: d_seq / d_flags are copies the final kernel makes (the host
+ * path: mapped host memory) -- the HMAC kernel keeps the decoded headers in
+ * the workspace; otherwise they are where the HMAC kernel decodes to.
+ */
+int decode_burst(const struct net2_burst_rx_keys *k, uint32_t ivlen,
+    const void *d_base, const uint64_t *d_offsets, const uint32_t *d_lens,
+    uint64_t n, uint8_t *d_result, void *d_iv, uint32_t *d_seq,
+    uint32_t *d_flags, void *d_ws, hipStream_t s, bool hdr_out, bool wave)
+{
+	const int hash_alg = k->hash_alg;
+	const int hash_set = hash_alg != NET2_HASH_NIL;
+	const bool alt = hash_set && k->alt_hash_key != nullptr;
+	BurstWs w;
+	burst_layout(n, (uint8_t *)d_ws, &w);
+	uint32_t *seq = d_seq && !hdr_out ? d_seq : w.seq;
+	uint32_t *flags = d_flags && !hdr_out ? d_flags : w.flags;
+	const int enc_set = k->enc_alg != 0;
+	if (hash_set) {
+		/* header decode, key choice, flag checks and HMAC verify in one
+		 * kernel over the wire datagrams (binned by datagram length) */
+		BurstArgs rx = {};
+		rx.seq = seq;
+		rx.flags = flags;
+		rx.status = w.status;
+		rx.enc_set = enc_set;
+		if (alt) {
+			const uint8_t *ak = (const uint8_t *)k->alt_hash_key;
+			rx.alt = 1;
+			rx.alt_enc_set = enc_set;
+			rx.no_cutoff = k->alt_no_cutoff != 0;
+			rx.cutoff = k->alt_cutoff;
+			rx.rx_start = k->rx_start;
+			for (size_t i = 0; i < k->alt_hash_keylen; i++)
+				rx.altkey[i / 4] |= (uint32_t)ak[i] << (24 - 8 * (i % 4));
+		}
+		if (wave) {
+			/* a small burst: 1 to 16 datagrams per workgroup,
+			 * codes, headers and IVs stored by that one launch */
+			rx.seq = d_seq;
+			rx.flags = d_flags;
+			rx.status = nullptr;
+			HIP_TRY(net2_launch_burst_wave(hash_alg,
+			    (const uint8_t *)k->hash_key, k->hash_keylen,
+			    (const uint8_t *)d_base, d_offsets, d_lens, n, &rx,
+			    d_result, enc_set ? (uint8_t *)d_iv : nullptr,
+			    enc_set ? ivlen : 0, nullptr, NET2_HMAC_MODE_BURST_RX,
+			    s));
+			FI_POINT(FI_KERNEL);
+			return 0;
+		}
+		HIP_TRY(net2_launch_hmac(hash_alg, (const uint8_t *)k->hash_key,
+		    k->hash_keylen, (const uint8_t *)d_base, d_offsets, d_lens, 0,
+		    0, n, w.verdict, burst_bins(n, w.bin), s,
+		    NET2_HMAC_MODE_BURST_RX, &rx));
+	} else {
+		HIP_TRY(net2_launch_burst_prep((uint8_t *)d_base, d_offsets,
+		    d_lens, n, 0, 0, enc_set, 0, nullptr, nullptr, seq,
+		    flags, w.sub_off, w.sub_len, w.status, s));
+	}
+	FI_POINT(FI_KERNEL);
+	HIP_TRY(net2_launch_burst_final(n, w.status, w.verdict, seq, flags,
+	    enc_set ? ivlen : 0, (uint8_t *)d_iv, d_result, s,
+	    hdr_out ? d_seq : nullptr, hdr_out ? d_flags : nullptr));
+	return 0;
+}
+
+/*
+ * The hash steps of net2_packet_encode for a device-resident burst.  rec
+ * (keyed hash only): header and hash field of every datagram to a record of
+ * their own (BurstArgs::rec) instead of into d_base.  bin: length-bin the
+ * burst at or above the threshold (burst_bins); the host path passes false
+ * where the order of the records matters more than the kernel's time.
+ */
+int encode_burst(int hash_alg, const void *hash_key, size_t hash_keylen,
+    int enc_alg, const uint32_t *d_seq, const uint32_t *d_flags,
+    void *d_base, const uint64_t *d_offsets, const uint32_t *d_lens,
+    uint64_t n, uint8_t *d_result, void *d_ws, hipStream_t s, bool wave,
+    uint8_t *rec, bool bin, uint8_t *seal_to)
+{
+	/* seal_to (keyed, no rec): headers and hash fields go there, at the
+	 * datagrams' offsets, instead of into d_base (the host path: the
+	 * caller's page-locked buffer through its device mapping) */
+	uint8_t *const out = seal_to != nullptr ? seal_to : (uint8_t *)d_base;
+	BurstWs w;
+	burst_layout(n, (uint8_t *)d_ws, &w);
+	if (hash_alg != NET2_HASH_NIL) {
+		/* flag and room checks, header write and HMAC sign in one
+		 * kernel over the wire datagrams; the TX code is final (no
+		 * verdict to fold in), so the kernel writes it to d_result */
+		BurstArgs tx = {};
+		tx.seq = const_cast<uint32_t *>(d_seq);
+		tx.flags = const_cast<uint32_t *>(d_flags);
+		tx.status = d_result;
+		tx.enc_set = enc_alg != 0;
+		tx.rec = rec;
+		if (wave) {
+			/* a small burst: 1 to 16 datagrams per workgroup */
+			HIP_TRY(net2_launch_burst_wave(hash_alg,
+			    (const uint8_t *)hash_key, hash_keylen,
+			    (const uint8_t *)d_base, d_offsets, d_lens, n, &tx,
+			    d_result, nullptr, 0, out, NET2_HMAC_MODE_BURST_TX, s));
+			FI_POINT(FI_KERNEL);
+			return 0;
+		}
+		HIP_TRY(net2_launch_hmac(hash_alg, (const uint8_t *)hash_key,
+		    hash_keylen, (const uint8_t *)d_base, d_offsets, d_lens, 0,
+		    0, n, out, bin ? burst_bins(n, w.bin) : nullptr, s,
+		    NET2_HMAC_MODE_BURST_TX, &tx));
+		FI_POINT(FI_KERNEL);
+		return 0;
+	}
+	HIP_TRY(net2_launch_burst_prep((uint8_t *)d_base, d_offsets,
+	    d_lens, n, 1, 0, enc_alg != 0, 0, d_seq, d_flags, nullptr,
+	    nullptr, w.sub_off, w.sub_len, w.status, s));
+	FI_POINT(FI_KERNEL);
+	HIP_TRY(net2_launch_burst_final(n, w.status, nullptr, d_seq, d_flags, 0,
+	    nullptr, d_result, s));
+	return 0;
+}
+
+NET2_EXPORT size_t net2_packet_burst_workspace(uint64_t n)
+{
+	return burst_layout(n, nullptr, nullptr);
+}
+
+NET2_EXPORT int net2_sha2_burst_limits(int64_t wave_max, int64_t bin_min)
+{
+	net2_set_burst_wave_max(wave_max);
+	g_burst_bin_min.store(bin_min < 0 ? -1 : bin_min, std::memory_order_relaxed);
+	return 0;
+}
+
+NET2_EXPORT int net2_packet_decode_burst_ck(const struct net2_burst_rx_keys *k,
+    uint32_t ivlen, const void *d_base, const uint64_t *d_offsets,
+    const uint32_t *d_lens, uint64_t n, uint8_t *d_result, void *d_iv,
+    uint32_t *d_seq, uint32_t *d_flags, void *d_ws, size_t ws_bytes,
+    void *stream)
+{
+	if (k == nullptr)
+		return EINVAL;
+	int rc = check_burst_args(k->hash_alg, k->hash_key, k->hash_keylen,
+	    ivlen, d_base, d_offsets, d_lens, n, d_result, d_ws, ws_bytes);
+	if (rc != 0)
+		return rc;
+	/* an alternate key is new key material under the same algorithms */
+	const bool alt = k->hash_alg != NET2_HASH_NIL &&
+	    k->alt_hash_key != nullptr;
+	if (alt && k->alt_hash_keylen != k->hash_keylen)
+		return EINVAL;
+	if (n == 0)
+		return 0;
+	if ((d_seq == nullptr) != (d_flags == nullptr))
+		return EINVAL;
+	return decode_burst(k, ivlen, d_base, d_offsets, d_lens, n, d_result,
+	    d_iv, d_seq, d_flags, d_ws, (hipStream_t)stream, false,
+	    n <= net2_burst_wave_max());
+}
+
+NET2_EXPORT int net2_packet_decode_burst(int hash_alg, const void *hash_key,
+    size_t hash_keylen, int enc_alg, uint32_t ivlen, const void *d_base,
+    const uint64_t *d_offsets, const uint32_t *d_lens, uint64_t n,
+    uint8_t *d_result, void *d_iv, uint32_t *d_seq, uint32_t *d_flags,
+    void *d_ws, size_t ws_bytes, void *stream)
+{
+	struct net2_burst_rx_keys k = {};
+	k.hash_alg = hash_alg;
+	k.hash_key = hash_key;
+	k.hash_keylen = hash_keylen;
+	k.enc_alg = enc_alg;
+	return net2_packet_decode_burst_ck(&k, ivlen, d_base, d_offsets, d_lens,
+	    n, d_result, d_iv, d_seq, d_flags, d_ws, ws_bytes, stream);
+}
+
+NET2_EXPORT int net2_packet_encode_burst(int hash_alg, const void *hash_key,
+    size_t hash_keylen, int enc_alg, const uint32_t *d_seq,
+    const uint32_t *d_flags, void *d_base, const uint64_t *d_offsets,
+    const uint32_t *d_lens, uint64_t n, uint8_t *d_result, void *d_ws,
+    size_t ws_bytes, void *stream)
+{
+	int rc = check_burst_args(hash_alg, hash_key, hash_keylen, 0, d_base,
+	    d_offsets, d_lens, n, d_result, d_ws, ws_bytes);
+	if (rc != 0 || n == 0)
+		return rc;
+	if (d_seq == nullptr || d_flags == nullptr)
+		return EINVAL;
+	return encode_burst(hash_alg, hash_key, hash_keylen, enc_alg, d_seq,
+	    d_flags, d_base, d_offsets, d_lens, n, d_result, d_ws,
+	    (hipStream_t)stream, n <= net2_burst_wave_max(), nullptr);
+}
+
+/* ---- the payload cipher of the bursts (aes_kernels.hip) -------------------- */
+
+NET2_EXPORT int net2_packet_decrypt_burst(const struct net2_burst_rx_keys *k,
+    const struct net2_burst_cipher_keys *ck, const void *d_base,
+    const uint64_t *d_offsets, const uint32_t *d_lens, uint64_t n,
+    const uint32_t *d_seq, const uint32_t *d_flags, const void *d_iv,
+    uint8_t *d_result, void *d_out, uint32_t *d_plen, void *stream)
+{
+	if (k == nullptr || check_cipher_keys(ck) != 0)
+		return EINVAL;
+	if (k->hash_alg != NET2_HASH_NIL && !hmac_row(k->hash_alg))
+		return EINVAL;
+	/* the alternate cipher key goes with the alternate hash key: the HMAC
+	 * step's choice of key set is the one made here */
+	const bool alt = k->alt_hash_key != nullptr;
+	if (alt && (k->hash_alg == NET2_HASH_NIL || ck->alt_enc_key == nullptr))
+		return EINVAL;
+	if (n == 0)
+		return 0;
+	if (!dgrams_ok(d_base, d_offsets, d_lens, n) || d_flags == nullptr ||
+	    d_iv == nullptr || d_result == nullptr || d_out == nullptr ||
+	    d_plen == nullptr || (alt && d_seq == nullptr))
+		return EINVAL;
+	if (int rc = check_current_device())
+		return rc;
+	const AesRxAlt ra = { alt ? (const uint8_t *)ck->alt_enc_key : nullptr,
+	    k->alt_no_cutoff, k->alt_cutoff, k->rx_start };
+	HIP_TRY(net2_launch_aes_decrypt((const uint8_t *)ck->enc_key, ra,
+	    k->hash_alg != NET2_HASH_NIL ? (uint32_t)digest_len(k->hash_alg) : 0,
+	    (const uint8_t *)d_base, d_offsets, d_lens, n, d_seq, d_flags,
+	    (const uint8_t *)d_iv, d_result, (uint8_t *)d_out, d_plen,
+	    (hipStream_t)stream));
+	return 0;
+}
+
+NET2_EXPORT int net2_packet_encrypt_burst(
+    const struct net2_burst_cipher_keys *ck, uint32_t hashlen,
+    const uint32_t *d_flags, const void *d_iv, void *d_base,
+    const uint64_t *d_offsets, const uint32_t *d_lens, const uint32_t *d_plen,
+    uint64_t n, uint8_t *d_result, uint32_t *d_wire_len, void *stream)
+{
+	if (check_cipher_keys(ck) != 0)
+		return EINVAL;
+	if (hashlen != 0 && hashlen != 32 && hashlen != 48 && hashlen != 64)
+		return EINVAL;
+	if (n == 0)
+		return 0;
+	if (!dgrams_ok(d_base, d_offsets, d_lens, n) || d_flags == nullptr ||
+	    d_iv == nullptr || d_plen == nullptr || d_result == nullptr ||
+	    d_wire_len == nullptr)
+		return EINVAL;
+	if (int rc = check_current_device())
+		return rc;
+	HIP_TRY(net2_launch_aes_encrypt((const uint8_t *)ck->enc_key, hashlen,
+	    d_flags, (const uint8_t *)d_iv, (uint8_t *)d_base, d_offsets, d_lens,
+	    d_plen, n, d_result, d_wire_len, (hipStream_t)stream));
+	return 0;
+}
+
+/* ---- keyed bursts over many connections: the device key table ------------- */
+
+/*
+ * The table of include/net2/packet.h: `slots` entries (Net2KeyEnt,
+ * sha2_launch.h) in the memory of the device that was current when it was
+ * made, all of one HMAC row.  Entries change only through the set / clear
+ * calls, each one launch in the caller's stream.
+ */
+struct net2_burst_keytab {
+	int device;
+	int hash_alg;
+	uint32_t slots;
+	Net2KeyEnt *ents;
+};
+
+namespace {
+
+/* Arguments first (by the caller), then: a usable device, and the table's. */
+int check_keytab_device(const struct net2_burst_keytab *tab)
+{
+	int cur = -1;
+	if (int rc = check_current_device())
+		return rc;
+	if (hipGetDevice(&cur) != hipSuccess)
+		return ENODEV;
+	return cur == tab->device ? 0 : EINVAL;
+}
+
+/* What the two _mc calls share: net2_packet_*_burst's checks with a table
+ * and a connection index per datagram in place of the key. */
+int check_burst_mc_args(const struct net2_burst_keytab *tab,
+    const uint32_t *d_conn, uint32_t ivlen, const void *d_base,
+    const uint64_t *d_offsets, const uint32_t *d_lens, uint64_t n,
+    const uint8_t *d_result, const void *d_ws, size_t ws_bytes,
+    bool hdr_pair_ok)
+{
+	if (tab == nullptr)
+		return EINVAL;
+	int rc = check_burst_arrays(ivlen, d_base, d_offsets, d_lens, n, d_result);
+	if (rc != 0 || n == 0)
+		return rc;
+	if (d_conn == nullptr || !hdr_pair_ok || !burst_ws_ok(d_ws, ws_bytes, n))
+		return EINVAL;
+	return check_keytab_device(tab);
+}
+
+}	/* namespace */
+
+NET2_EXPORT int net2_burst_keytab_create(int hash_alg, uint32_t slots,
+    struct net2_burst_keytab **tab)
+{
+	if (tab == nullptr)
+		return EINVAL;
+	*tab = nullptr;
+	if (!hmac_row(hash_alg) || slots == 0)
+		return EINVAL;
+	if (int rc = check_current_device())
+		return rc;
+	std::unique_ptr<net2_burst_keytab> t(new (std::nothrow) net2_burst_keytab());
+	if (!t)
+		return ENOMEM;
+	if (hipGetDevice(&t->device) != hipSuccess)
+		return ENODEV;
+	t->hash_alg = hash_alg;
+	t->slots = slots;
+	const size_t bytes = (size_t)slots * sizeof(Net2KeyEnt);
+	HIP_TRY(hipMalloc((void **)&t->ents, bytes));
+	/* every slot unset before the first call that could read it, whatever
+	 * stream that call uses */
+	hipError_t e = hipMemset(t->ents, 0, bytes);
+	if (e == hipSuccess)
+		e = hipDeviceSynchronize();
+	if (e != hipSuccess) {
+		(void)hipFree(t->ents);
+		return hip_fail(e);
+	}
+	*tab = t.release();
+	return 0;
+}
+
+NET2_EXPORT void net2_burst_keytab_destroy(struct net2_burst_keytab *tab)
+{
+	if (tab == nullptr)
+		return;
+	/* (hipFree waits for the work that may still read the entries) */
+	(void)hipFree(tab->ents);
+	delete tab;
+}
+
+NET2_EXPORT int net2_burst_keytab_set_rx(struct net2_burst_keytab *tab,
+    uint32_t slot, const struct net2_burst_rx_keys *keys, void *stream)
+{
+	if (tab == nullptr || keys == nullptr || slot >= tab->slots)
+		return EINVAL;
+	if (keys->hash_alg != tab->hash_alg || keys->hash_key == nullptr ||
+	    keys->hash_keylen != (size_t)kRows[tab->hash_alg].keylen)
+		return EINVAL;
+	const bool alt = keys->alt_hash_key != nullptr;
+	if (alt && keys->alt_hash_keylen != keys->hash_keylen)
+		return EINVAL;
+	if (int rc = check_keytab_device(tab))
+		return rc;
+	const uint32_t bits = NET2_KT_RX | (keys->enc_alg != 0 ? NET2_KT_RX_ENC : 0) |
+	    (alt ? NET2_KT_RX_ALT : 0) |
+	    (alt && keys->alt_no_cutoff != 0 ? NET2_KT_RX_NOCUT : 0);
+	HIP_TRY(net2_launch_keytab_set(tab->hash_alg, tab->ents + slot, NET2_KT_RX,
+	    (const uint8_t *)keys->hash_key, (const uint8_t *)keys->alt_hash_key,
+	    keys->hash_keylen, bits, alt ? keys->alt_cutoff : 0,
+	    alt ? keys->rx_start : 0, (hipStream_t)stream));
+	return 0;
+}
+
+NET2_EXPORT int net2_burst_keytab_set_tx(struct net2_burst_keytab *tab,
+    uint32_t slot, const void *key, size_t keylen, int enc_alg, void *stream)
+{
+	if (tab == nullptr || key == nullptr || slot >= tab->slots ||
+	    keylen != (size_t)kRows[tab->hash_alg].keylen)
+		return EINVAL;
+	if (int rc = check_keytab_device(tab))
+		return rc;
+	HIP_TRY(net2_launch_keytab_set(tab->hash_alg, tab->ents + slot, NET2_KT_TX,
+	    (const uint8_t *)key, nullptr, keylen,
+	    NET2_KT_TX | (enc_alg != 0 ? NET2_KT_TX_ENC : 0), 0, 0,
+	    (hipStream_t)stream));
+	return 0;
+}
+
+NET2_EXPORT int net2_burst_keytab_clear(struct net2_burst_keytab *tab,
+    uint32_t slot, void *stream)
+{
+	if (tab == nullptr || slot >= tab->slots)
+		return EINVAL;
+	if (int rc = check_keytab_device(tab))
+		return rc;
+	HIP_TRY(net2_launch_keytab_set(tab->hash_alg, tab->ents + slot, 0, nullptr,
+	    nullptr, 0, 0, 0, 0, (hipStream_t)stream));
+	return 0;
+}
+
+NET2_EXPORT int net2_packet_decode_burst_mc(const struct net2_burst_keytab *tab,
+    const uint32_t *d_conn, uint32_t ivlen, const void *d_base,
+    const uint64_t *d_offsets, const uint32_t *d_lens, uint64_t n,
+    uint8_t *d_result, void *d_iv, uint32_t *d_seq, uint32_t *d_flags,
+    void *d_ws, size_t ws_bytes, void *stream)
+{
+	int rc = check_burst_mc_args(tab, d_conn, ivlen, d_base, d_offsets,
+	    d_lens, n, d_result, d_ws, ws_bytes,
+	    (d_seq == nullptr) == (d_flags == nullptr));
+	if (rc != 0 || n == 0)
+		return rc;
+	hipStream_t s = (hipStream_t)stream;
+	BurstWs w;
+	burst_layout(n, (uint8_t *)d_ws, &w);
+	/* as decode_burst's keyed lane form: the HMAC kernel decodes the
+	 * headers to where the caller wants them (else the workspace) ... */
+	BurstArgs rx = {};
+	rx.seq = d_seq != nullptr ? d_seq : w.seq;
+	rx.flags = d_flags != nullptr ? d_flags : w.flags;
+	rx.status = w.status;
+	const KeyTabArgs kt = { d_conn, tab->ents, tab->slots };
+	HIP_TRY(net2_launch_hmac_mc(tab->hash_alg, kt, (const uint8_t *)d_base,
+	    d_offsets, d_lens, n, w.verdict, burst_bins(n, w.bin), s,
+	    NET2_HMAC_MODE_BURST_RX, rx));
+	FI_POINT(FI_KERNEL);
+	/* ... and the final kernel folds the verdicts in and derives the IV
+	 * of every OK PH_ENCRYPTED datagram whose connection has a cipher key
+	 * (one cipher, so one ivlen) */
+	HIP_TRY(net2_launch_burst_final_mc(n, w.status, w.verdict, rx.seq,
+	    rx.flags, ivlen, (uint8_t *)d_iv, d_result, s));
+	return 0;
+}
+
+NET2_EXPORT int net2_packet_encode_burst_mc(const struct net2_burst_keytab *tab,
+    const uint32_t *d_conn, const uint32_t *d_seq, const uint32_t *d_flags,
+    void *d_base, const uint64_t *d_offsets, const uint32_t *d_lens,
+    uint64_t n, uint8_t *d_result, void *d_ws, size_t ws_bytes, void *stream)
+{
+	int rc = check_burst_mc_args(tab, d_conn, 0, d_base, d_offsets, d_lens, n,
+	    d_result, d_ws, ws_bytes, d_seq != nullptr && d_flags != nullptr);
+	if (rc != 0 || n == 0)
+		return rc;
+	BurstWs w;
+	burst_layout(n, (uint8_t *)d_ws, &w);
+	BurstArgs tx = {};
+	tx.seq = const_cast<uint32_t *>(d_seq);
+	tx.flags = const_cast<uint32_t *>(d_flags);
+	tx.status = d_result;		/* the TX code is final in the kernel */
+	const KeyTabArgs kt = { d_conn, tab->ents, tab->slots };
+	HIP_TRY(net2_launch_hmac_mc(tab->hash_alg, kt, (const uint8_t *)d_base,
+	    d_offsets, d_lens, n, (uint8_t *)d_base, burst_bins(n, w.bin),
+	    (hipStream_t)stream, NET2_HMAC_MODE_BURST_TX, tx));
+	FI_POINT(FI_KERNEL);
+	return 0;
+}

@@ -54,7 +54,7 @@ void stats(size_t idx, uint64_t *calls, uint64_t *launches);
 
 /*
  * submit() on the calling thread's current HIP device if it is a gfx950,
- * else on the first one (sha2_shim.cpp); ENODEV without one.  Records the
+ * else on the first one (net2_single.cpp); ENODEV without one.  Records the
  * HIP error of an EIO for net2_sha2_last_hip_error().
  */
 int net2_co_run(const net2co::Request &r);

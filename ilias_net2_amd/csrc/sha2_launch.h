@@ -1,6 +1,6 @@
 /*
- * sha2_launch.h -- internal interface between the C-ABI shim (sha2_shim.cpp)
- * and the kernels (sha2_kernels.hip).  Not installed; the public surface is
+ * sha2_launch.h -- internal interface between the host units behind the C ABI
+ * (net2_host.h) and the kernels (sha2_kernels.hip).  Not installed; the public surface is
  * include/net2/sha2_batch.h and include/net2/hash.h.
  */
 #ifndef NET2_SHA2_LAUNCH_H

@@ -4,8 +4,8 @@ Packets are independent, so a global batch is split into
 contiguous slices with no data-path collective; each rank hashes its slice on
 its own device.  The byte-balanced split for variable-length batches is the
 same rule the C ABI's multi-device ``net2_sha2_batch`` uses
-(csrc/sha2_shim.cpp): device d starts at the first packet whose running byte
-count reaches d/N of the total.
+(shard_batch, csrc/net2_host.h): device d starts at the first packet whose
+running byte count reaches d/N of the total.
 """
 from __future__ import annotations
 

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Build an A/B variant of libnet2_sha2.so: tools/ab/<name>.so from
 # sha2_kernels.hip compiled with the given -D flags, linked with the
-# in-tree shim objects (make -C ilias_net2_amd/csrc first).
+# in-tree host objects (make -C ilias_net2_amd/csrc first).
 #   tools/build_ab.sh a1pf0 -DNET2_VAR_A1_PREFETCH=0
 set -eu
 name=$1; shift
@@ -17,7 +17,8 @@ ID=$(sha256sum $HERE/ab/$name.fatbin | cut -c1-16)
 /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC -fvisibility=hidden -DNET2_KERNEL_BUILD_ID="\"$ID\"" \
     -c $SRC/sha2_buildid.cpp -o $HERE/ab/$name.bid.o
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $HERE/ab/$name.so \
-    $HERE/ab/$name.o $HERE/ab/$name.bid.o $SRC/build/sha2_shim.o $SRC/build/sha2_coalesce.o \
-    $SRC/build/sha2_stream.o -lpthread
+    $HERE/ab/$name.o $HERE/ab/$name.bid.o $SRC/build/net2_runtime.o $SRC/build/net2_batch.o \
+    $SRC/build/net2_single.o $SRC/build/net2_dgram.o $SRC/build/net2_burst_host.o \
+    $SRC/build/sha2_coalesce.o $SRC/build/sha2_stream.o -lpthread
 rm -f $HERE/ab/$name.o $HERE/ab/$name.bid.o $HERE/ab/$name.fatbin
 echo built $HERE/ab/$name.so "(build id $ID)"

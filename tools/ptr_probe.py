@@ -26,7 +26,7 @@ def show(name, p):
           f"devptr={a.devicePointer or 0:#x} hostptr={a.hostPointer or 0:#x} "
           f"flags={a.allocationFlags:#x} | getdevptr rc={rc2} dp={dp.value or 0:#x} "
           f"delta={(dp.value or 0) - p}", flush=True)
-    # allocation range / buffer id (sha2_shim.cpp pinned_span)
+    # allocation range / buffer id (net2_runtime.cpp pinned_span)
     for nm, code in (("RANGE_START_ADDR", 11), ("RANGE_SIZE", 12), ("BUFFER_ID", 7)):
         v = ctypes.c_uint64(0)
         rc3 = hip.hipPointerGetAttribute(ctypes.byref(v), ctypes.c_int(code),
