@@ -7,6 +7,12 @@ its hash burst: AES-256-CBC with PKCS#7 padding, the reference's ``aes256``
 what OpenSSL's EVP computes.  PyTorch owns the memory and the streams; the
 work is the HIP kernels behind ``net2_packet_{decrypt,encrypt}_burst``
 (include/net2/packet.h).
+
+For a burst that interleaves many connections, ``CipherTable`` mirrors
+``struct net2_burst_ciphertab`` -- every connection's cipher keys on the
+device, one slot per connection, beside ``conn_burst.KeyTable`` -- and
+``decrypt_burst_mc`` / ``encrypt_burst_mc`` run each datagram under the keys
+of slot ``conn[i]`` in one call.
 """
 from __future__ import annotations
 
@@ -114,4 +120,153 @@ def encrypt_burst(key: bytes, hashlen: int, flags, iv, data, offsets, lens,
         n, res.data_ptr(), wire.data_ptr(), s.cuda_stream)
     del keep
     check(rc, "net2_packet_encrypt_burst")
+    return res, wire
+
+
+# ---- the cipher over many connections -----------------------------------------
+
+NOCONN = 5          # NET2_PBURST_NOCONN
+
+
+class CipherTable:
+    """A device cipher-key table of ``slots`` connections (AES-256-CBC), on
+    ``device`` (default: torch's current device): ``struct
+    net2_burst_ciphertab`` (include/net2/packet.h), the companion of
+    ``conn_burst.KeyTable`` under the same ``conn`` indices.  Updates are
+    asynchronous on ``stream`` and ordered with the bursts there."""
+
+    def __init__(self, slots: int, device=None):
+        import torch
+        self._tab = ctypes.c_void_p()
+        self.slots = slots
+        self.device = torch.device("cuda", torch.cuda.current_device()
+                                   if device is None else
+                                   torch.device(device).index or 0)
+        with torch.cuda.device(self.device):
+            check(_lib.lib().net2_burst_ciphertab_create(
+                _lib.ENC_AES256, slots, ctypes.byref(self._tab)),
+                "net2_burst_ciphertab_create")
+
+    @property
+    def ptr(self) -> int:
+        if not self._tab:
+            raise ValueError("the cipher table is closed")
+        return self._tab.value
+
+    def _stream(self, stream):
+        return _launch_stream(stream, self.device).cuda_stream
+
+    def set_rx(self, slot: int, key: bytes, hash_alg: int = 0,
+               alt_key: Optional[bytes] = None, alt_no_cutoff: bool = False,
+               alt_cutoff: int = 0, rx_start: int = 0, stream=None) -> None:
+        """The slot's rx side: the connection's cipher key and, during a
+        rollover, the alternate key with the cutoff arguments its hash keys
+        were set with (``hash_alg``: the connection's keyed hash; an
+        alternate key needs one)."""
+        import torch
+        ck, keep = _cipher_keys(key, alt_key)
+        rk = _lib.BurstRxKeys(hash_alg, None, 0, _lib.ENC_AES256,
+                              ck.alt_enc_key, 0, int(bool(alt_no_cutoff)),
+                              alt_cutoff & 0xffffffff, rx_start & 0xffffffff)
+        with torch.cuda.device(self.device):
+            rc = _lib.lib().net2_burst_ciphertab_set_rx(
+                self.ptr, slot, ctypes.byref(rk), ctypes.byref(ck),
+                self._stream(stream))
+        del keep
+        check(rc, "net2_burst_ciphertab_set_rx")
+
+    def set_tx(self, slot: int, key: bytes, stream=None) -> None:
+        """The slot's tx side: the key the transmitter encrypts with."""
+        import torch
+        ck, keep = _cipher_keys(key, None)
+        with torch.cuda.device(self.device):
+            rc = _lib.lib().net2_burst_ciphertab_set_tx(
+                self.ptr, slot, ctypes.byref(ck), self._stream(stream))
+        del keep
+        check(rc, "net2_burst_ciphertab_set_tx")
+
+    def clear(self, slot: int, stream=None) -> None:
+        """Both sides of the slot unset."""
+        import torch
+        with torch.cuda.device(self.device):
+            check(_lib.lib().net2_burst_ciphertab_clear(
+                self.ptr, slot, self._stream(stream)),
+                "net2_burst_ciphertab_clear")
+
+    def close(self) -> None:
+        if self._tab:
+            _lib.lib().net2_burst_ciphertab_destroy(self._tab)
+            self._tab = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _conn_arg(conn, n):
+    import torch
+    _need(conn, torch.int32, "conn")
+    if conn.numel() != n:
+        raise ValueError("conn must have one entry per datagram")
+
+
+def decrypt_burst_mc(table: CipherTable, conn, hashlen: int, data, offsets, lens,
+                     seq, flags, iv, result, out=None, stream=None):
+    """``decrypt_burst`` under the rx keys of slot conn[i] (int32 CUDA tensor,
+    read as uint32) of ``table``; ``hashlen`` is the digest length of the hash
+    burst's row (0: none).  An OK PH_ENCRYPTED datagram without a connection
+    becomes NOCONN.  Returns (result, out, plen int32[n]); asynchronous on
+    ``stream``."""
+    import torch
+    n = _burst_args(data, offsets, lens, flags, iv)
+    _conn_arg(conn, n)
+    _need(seq, torch.int32, "seq")
+    _need(result, torch.uint8, "result")
+    if seq.numel() != n or result.numel() != n:
+        raise ValueError("seq and result must have one entry per datagram")
+    s = _launch_stream(stream, data.device)
+    with torch.cuda.stream(s):
+        if out is None:
+            out = torch.empty_like(data)
+        plen = torch.empty((n,), dtype=torch.int32, device=data.device)
+    _need(out, torch.uint8, "out")
+    if out.numel() < data.numel():
+        raise ValueError("out is smaller than the burst")
+    rc = _lib.lib().net2_packet_decrypt_burst_mc(
+        table.ptr, conn.data_ptr(), hashlen, data.data_ptr(), offsets.data_ptr(),
+        lens.data_ptr(), n, seq.data_ptr(), flags.data_ptr(), iv.data_ptr(),
+        result.data_ptr(), out.data_ptr(), plen.data_ptr(), s.cuda_stream)
+    check(rc, "net2_packet_decrypt_burst_mc")
+    return result, out, plen
+
+
+def encrypt_burst_mc(table: CipherTable, conn, hashlen: int, flags, iv, data,
+                     offsets, lens, plen, stream=None):
+    """``encrypt_burst`` under the tx key of slot conn[i] of ``table``.  A
+    PH_ENCRYPTED slot with room but without a connection is NOCONN, untouched,
+    wire_len 0.  Returns (result uint8[n], wire_len int32[n]); asynchronous on
+    ``stream``."""
+    import torch
+    n = _burst_args(data, offsets, lens, flags, iv)
+    _conn_arg(conn, n)
+    _need(plen, torch.int32, "plen")
+    if plen.numel() != n:
+        raise ValueError("plen must have one entry per datagram")
+    s = _launch_stream(stream, data.device)
+    with torch.cuda.stream(s):
+        res = torch.empty((n,), dtype=torch.uint8, device=data.device)
+        wire = torch.empty((n,), dtype=torch.int32, device=data.device)
+    rc = _lib.lib().net2_packet_encrypt_burst_mc(
+        table.ptr, conn.data_ptr(), hashlen, flags.data_ptr(), iv.data_ptr(),
+        data.data_ptr(), offsets.data_ptr(), lens.data_ptr(), plen.data_ptr(),
+        n, res.data_ptr(), wire.data_ptr(), s.cuda_stream)
+    check(rc, "net2_packet_encrypt_burst_mc")
     return res, wire

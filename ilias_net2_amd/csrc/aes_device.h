@@ -166,4 +166,18 @@ AES_HD uint32_t aes_pkcs7_pad(const uint32_t (&p)[4])
 	return ok ? v : 0u;
 }
 
+/*
+ * net2_ck_rx_key (src/conn_keys.c:447-476) for one datagram: true when it
+ * takes the alternate rx key.  installed: an alternate key is there
+ * (NET2_CK_RX_ALT); no_cutoff: NET2_CK_F_NO_RX_CUTOFF; fl, seq: the
+ * datagram's header; rx_start: the window's cw_rx_start.  32-bit wrap-around
+ * arithmetic, as the reference's.
+ */
+AES_HD bool aes_rx_alt(bool installed, bool no_cutoff, uint32_t fl,
+    uint32_t seq, uint32_t cutoff, uint32_t rx_start)
+{
+	return installed && ((fl & 0x80000000u /* PH_ALTKEY */) != 0 ||
+	    (!no_cutoff && seq - rx_start >= cutoff - rx_start));
+}
+
 #endif /* NET2_AES_DEVICE_H */

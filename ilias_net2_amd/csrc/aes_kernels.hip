@@ -25,6 +25,8 @@
  * stay in scalar registers.  With an alternate rx key installed the choice
  * is per datagram, so that instance copies both schedules to LDS (the second
  * 272 bytes after the first: another bank) and each lane reads its own.
+ * The _mc kernels (further down) take each datagram's keys from its own
+ * connection's entry of a device table instead.
  *
  * Payloads start at 8, 40, 56 or 72 bytes past an arbitrary offset, so blocks
  * are moved with 16-byte global accesses at byte alignment (the unaligned
@@ -34,7 +36,9 @@
 #include "aes_device.h"
 #include "aes_launch.h"
 #include "aes_sched.h"
+#include "aes_tab.h"
 
+#include <stddef.h>
 #include <string.h>
 
 namespace {
@@ -42,7 +46,6 @@ namespace {
 constexpr uint32_t PKT_HDR = 8;			/* net2_ph_overhead */
 constexpr uint32_t PKT_PH_ENCRYPTED = 0x00000001u;
 constexpr uint32_t PKT_PH_SIGNED = 0x00000002u;
-constexpr uint32_t PKT_PH_ALTKEY = 0x80000000u;
 constexpr uint8_t PKT_OK = 0, PKT_RESOURCE = 1, PKT_BAD = 2;
 
 constexpr int AES_WG = 256;		/* lanes per workgroup = table entries */
@@ -240,8 +243,8 @@ __global__ __launch_bounds__(AES_WG) void aes_cbc_decrypt_kernel(
 	const uint32_t po = payload_at(fl, a.hashlen);
 	const LdsTab T = { tab + (threadIdx.x & (AES_REP - 1)) };
 	/* net2_ck_rx_key (src/conn_keys.c:447-476), as the HMAC step chose */
-	const bool alt = ALT && ((fl & PKT_PH_ALTKEY) != 0 || (a.no_cutoff == 0 &&
-	    a.seq[i] - a.rx_start >= a.cutoff - a.rx_start));
+	const bool alt = ALT && aes_rx_alt(true, a.no_cutoff != 0, fl, a.seq[i],
+	    a.cutoff, a.rx_start);
 	const RkLds KL = { rks + (alt ? AES_RK_STRIDE : 0) };
 	const RkArgs KA = { keys.k[0] };
 	const uint64_t off = a.offsets[i] + po;
@@ -373,6 +376,297 @@ __global__ __launch_bounds__(AES_WG) void aes_cbc_encrypt_kernel(
 	}
 }
 
+/*
+ * The same under the keys of each datagram's own connection
+ * (net2_packet_{decrypt,encrypt}_burst_mc): datagram i belongs to slot conn[i]
+ * of the device cipher-key table (Net2CipherEnt, aes_tab.h).  What needs no
+ * cipher work is settled by the datagram's own lane before the ranking, as
+ * above; a datagram with cipher work but without a connection -- conn[i] out
+ * of range, or the slot's rx (decrypt) / tx (encrypt) side unset -- is
+ * PKT_NOCONN there and left untouched: one conn load and one meta load.  An
+ * index out of range is clamped to entry 0 before any address is formed from
+ * it.  After the ranking lane t looks up the entry of the datagram it owns
+ * and takes its schedule from there (RX: the active or the alternate one,
+ * picked by address).
+ *
+ * Round keys: a lane loads the 60 words of its schedule once, as fifteen
+ * 16-byte global loads, and holds them in VGPRs for all its blocks (RkRegs;
+ * the rounds are unrolled, so every index is a constant).  With
+ * -DNET2_AES_MC_REREAD=1 it reads them from the table again in every block
+ * instead (RkGlobal): fewer registers, fifteen scattered loads per lane and
+ * block.  DESIGN.md 5.5.4 has both forms' numbers.
+ */
+#ifndef NET2_AES_MC_REREAD
+#define NET2_AES_MC_REREAD 0
+#endif
+constexpr uint8_t PKT_NOCONN = 5;	/* NET2_PBURST_NOCONN */
+
+struct AesMcArgs {
+	AesBurstArgs b;
+	const uint32_t *conn;
+	const Net2CipherEnt *tab;
+	uint32_t slots;
+};
+
+/* Round keys out of a table entry's schedule (16-byte aligned): loaded once
+ * into the lane's registers, or read from the table at every use. */
+struct RkRegs {
+	uint32_t w[NET2_AES_RKWORDS];
+	__device__ __forceinline__ explicit RkRegs(const uint32_t *p)
+	{
+		const u32x4 *q = reinterpret_cast<const u32x4 *>(p);
+#pragma unroll
+		for (int k = 0; k < NET2_AES_RKWORDS / 4; k++) {
+			const u32x4 v = q[k];
+			w[4 * k] = v.x;
+			w[4 * k + 1] = v.y;
+			w[4 * k + 2] = v.z;
+			w[4 * k + 3] = v.w;
+		}
+	}
+	__device__ __forceinline__ uint32_t operator()(int i) const
+	{
+		return w[i];
+	}
+};
+struct RkGlobal {
+	const uint32_t *p;	/* a schedule in the table, 16-byte aligned */
+	__device__ __forceinline__ explicit RkGlobal(const uint32_t *q) :
+	    p((const uint32_t *)__builtin_assume_aligned(q, 16)) {}
+	__device__ __forceinline__ uint32_t operator()(int i) const
+	{
+		return p[i];
+	}
+};
+#if NET2_AES_MC_REREAD
+typedef RkGlobal RkMc;
+#else
+typedef RkRegs RkMc;
+#endif
+
+/* The entry of datagram i; *in: its index was in range (else entry 0). */
+__device__ __forceinline__ const Net2CipherEnt *ciphertab_ent(
+    const AesMcArgs &m, uint64_t i, bool *in)
+{
+	const uint32_t c = m.conn[i];
+	*in = c < m.slots;
+	return m.tab + (*in ? c : 0u);
+}
+
+/* Whether datagram i's slot has `side` (NET2_CT_RX / NET2_CT_TX) set. */
+__device__ __forceinline__ bool ciphertab_has(const AesMcArgs &m, uint64_t i,
+    uint32_t side)
+{
+	bool in;
+	const Net2CipherEnt *e = ciphertab_ent(m, i, &in);
+	return in && (e->meta[0] & side) != 0;
+}
+
+/* decrypt_prep, after the connection check of a datagram that would be
+ * decrypted (no look-up for any other). */
+__device__ __forceinline__ uint32_t decrypt_mc_prep(const AesMcArgs &m,
+    uint64_t i)
+{
+	const AesBurstArgs &a = m.b;
+	if (i < a.n && a.result[i] == PKT_OK &&
+	    (a.flags[i] & PKT_PH_ENCRYPTED) != 0 && !ciphertab_has(m, i, NET2_CT_RX)) {
+		a.result[i] = PKT_NOCONN;
+		a.plen[i] = 0;
+		return 0;
+	}
+	return decrypt_prep(a, i);
+}
+
+/* encrypt_prep, then the connection check of a slot it found room to encrypt
+ * (RESOURCE wins over NOCONN; no look-up for any other). */
+__device__ __forceinline__ uint32_t encrypt_mc_prep(const AesMcArgs &m,
+    uint64_t i)
+{
+	const AesBurstArgs &a = m.b;
+	const uint32_t nb = encrypt_prep(a, i);
+	if (nb != 0 && !ciphertab_has(m, i, NET2_CT_TX)) {
+		a.result[i] = PKT_NOCONN;
+		a.wire_len[i] = 0;
+		return 0;
+	}
+	return nb;
+}
+
+__global__ __launch_bounds__(AES_WG) void aes_cbc_decrypt_mc_kernel(
+    const AesMcArgs m)
+{
+	__shared__ uint32_t tab[256 * AES_REP > 2 * AES_WG ? 256 * AES_REP :
+	    2 * AES_WG];
+
+	const AesBurstArgs &a = m.b;
+	const uint64_t first = (uint64_t)blockIdx.x * AES_WG;
+	uint32_t nb;
+	const uint64_t i = first + lanes_by_work(tab,
+	    decrypt_mc_prep(m, first + threadIdx.x), &nb);
+	aes_build_table<true>(tab);
+	if (nb == 0)
+		return;
+
+	const uint32_t fl = a.flags[i];
+	const uint32_t po = payload_at(fl, a.hashlen);
+	const LdsTab T = { tab + (threadIdx.x & (AES_REP - 1)) };
+	bool in;
+	const Net2CipherEnt *e = ciphertab_ent(m, i, &in);
+	const u32x4 mt = *reinterpret_cast<const u32x4 *>(e->meta);
+	const bool alt = aes_rx_alt((mt.x & NET2_CT_RX_ALT) != 0,
+	    (mt.x & NET2_CT_RX_NOCUT) != 0, fl, a.seq[i], mt.y, mt.z);
+	const RkMc K(e->dec[alt ? 1 : 0]);
+	const uint64_t off = a.offsets[i] + po;
+	const uint8_t *src = a.in + off;
+	uint8_t *dst = a.out + off;
+	uint32_t ivw[4], c[4], prev[4];
+	uint32_t b = nb - 1, pad = 0;
+
+	/* the block order and the loads of aes_cbc_decrypt_kernel */
+	ld16(a.iv + NET2_AES_BLOCK * i, ivw);
+	ld16(src + 16 * (uint64_t)b, c);
+	if (nb > 1) {
+		ld16(src + 16 * (uint64_t)(b - 1), prev);
+	} else {
+#pragma unroll
+		for (int k = 0; k < 4; k++)
+			prev[k] = ivw[k];
+	}
+	for (uint32_t j = 0; j < nb; j++) {
+		const uint32_t bn = j == 0 ? 0u : b + 1;
+		uint32_t cn[4] = { 0, 0, 0, 0 };
+		if (j + 1 < nb)
+			ld16(src + 16 * (uint64_t)bn, cn);
+		uint32_t x[4] = { c[0], c[1], c[2], c[3] };
+		aes_block<true>(T, K, x);
+#pragma unroll
+		for (int k = 0; k < 4; k++)
+			x[k] ^= prev[k];
+		if (j == 0) {
+			pad = aes_pkcs7_pad(x);
+			if (pad == 0)
+				break;
+		}
+		st16(dst + 16 * (uint64_t)b, x);
+#pragma unroll
+		for (int k = 0; k < 4; k++) {
+			prev[k] = j == 0 ? ivw[k] : c[k];
+			c[k] = cn[k];
+		}
+		b = bn;
+	}
+	if (pad == 0)
+		a.result[i] = PKT_BAD;
+	a.plen[i] = pad != 0 ? 16 * nb - pad : 0u;
+}
+
+__global__ __launch_bounds__(AES_WG) void aes_cbc_encrypt_mc_kernel(
+    const AesMcArgs m)
+{
+	__shared__ uint32_t tab[256 * AES_REP > 2 * AES_WG ? 256 * AES_REP :
+	    2 * AES_WG];
+
+	const AesBurstArgs &a = m.b;
+	const uint64_t first = (uint64_t)blockIdx.x * AES_WG;
+	uint32_t nb;
+	const uint64_t i = first + lanes_by_work(tab,
+	    encrypt_mc_prep(m, first + threadIdx.x), &nb);
+	aes_build_table<false>(tab);
+	if (nb == 0)
+		return;
+
+	const LdsTab T = { tab + (threadIdx.x & (AES_REP - 1)) };
+	bool in;
+	const RkMc K(ciphertab_ent(m, i, &in)->enc);
+	uint8_t *p = a.out + a.offsets[i] + payload_at(a.flags[i], a.hashlen);
+	const uint32_t rem = a.plen[i] & 15u;
+	uint32_t chain[4], cur[4];
+
+	/* block j of the padded plaintext, as in aes_cbc_encrypt_kernel */
+	auto load = [&](uint32_t j, uint32_t (&w)[4]) {
+		const uint8_t *q = p + 16 * (uint64_t)j;
+		if (j + 1 < nb) {
+			ld16(q, w);
+			return;
+		}
+		w[0] = w[1] = w[2] = w[3] = 0;
+#pragma unroll
+		for (uint32_t k = 0; k < 16; k++) {
+			const uint32_t v = k < rem ? q[k] : 16u - rem;
+			w[k / 4] |= v << (24 - 8 * (k % 4));
+		}
+	};
+
+	ld16(a.iv + NET2_AES_BLOCK * i, chain);
+	load(0, cur);
+	for (uint32_t j = 0; j < nb; j++) {
+		uint32_t nx[4] = { 0, 0, 0, 0 };
+		if (j + 1 < nb)
+			load(j + 1, nx);
+#pragma unroll
+		for (int k = 0; k < 4; k++)
+			chain[k] ^= cur[k];
+		aes_block<false>(T, K, chain);
+		st16(p + 16 * (uint64_t)j, chain);
+#pragma unroll
+		for (int k = 0; k < 4; k++)
+			cur[k] = nx[k];
+	}
+}
+
+/*
+ * One slot's update (net2_burst_ciphertab_set_rx / _set_tx / _clear): the new
+ * entry arrives by value and one wave stores it, 16 bytes per lane (the
+ * argument is read with constant indices only and selected per lane: a
+ * dynamic index would copy it to scratch).  Piece 0 is the meta words, 1..30
+ * the two rx schedules, 31..45 the tx schedule.  side NET2_AES_TAB_RX stores
+ * the rx pieces and replaces the rx bits, cutoff and rx_start;
+ * NET2_AES_TAB_TX the tx pieces and the tx bit; 0 zeroes the entry.  Stream
+ * order is the only synchronisation an entry has.
+ */
+constexpr unsigned CT_PIECES = sizeof(Net2CipherEnt) / 16;
+constexpr unsigned CT_TX_FIRST = offsetof(Net2CipherEnt, enc) / 16;
+
+__global__ __launch_bounds__(64) void aes_tab_set_kernel(Net2CipherEnt *ent,
+    uint32_t side, const Net2CipherEnt nw)
+{
+	if (blockIdx.x != 0)
+		return;
+	const unsigned t = threadIdx.x;
+	u32x4 *q = reinterpret_cast<u32x4 *>(ent);
+	const uint32_t *w = reinterpret_cast<const uint32_t *>(&nw);
+	u32x4 v = { 0, 0, 0, 0 };
+#pragma unroll
+	for (unsigned k = 1; k < CT_PIECES; k++)
+		if (t == k) {
+			v.x = w[4 * k];
+			v.y = w[4 * k + 1];
+			v.z = w[4 * k + 2];
+			v.w = w[4 * k + 3];
+		}
+	const bool rx_piece = t >= 1 && t < CT_TX_FIRST;
+	const bool tx_piece = t >= CT_TX_FIRST && t < CT_PIECES;
+	if ((side == NET2_AES_TAB_RX && rx_piece) ||
+	    (side == NET2_AES_TAB_TX && tx_piece) ||
+	    (side == 0 && (rx_piece || tx_piece)))
+		q[t] = v;
+	/* lane 63: the meta words, the other side's bits kept */
+	if (t == 63) {
+		u32x4 mt = q[0];
+		if (side == NET2_AES_TAB_RX) {
+			mt.x = (mt.x & NET2_CT_TX_BITS) | (nw.meta[0] & NET2_CT_RX_BITS);
+			mt.y = nw.meta[1];
+			mt.z = nw.meta[2];
+			mt.w = 0;
+		} else if (side == NET2_AES_TAB_TX) {
+			mt.x = (mt.x & NET2_CT_RX_BITS) | (nw.meta[0] & NET2_CT_TX_BITS);
+		} else {
+			mt = u32x4{ 0, 0, 0, 0 };
+		}
+		q[0] = mt;
+	}
+}
+
 void wipe(void *p, size_t n)
 {
 	volatile uint8_t *z = (volatile uint8_t *)p;
@@ -446,5 +740,75 @@ hipError_t net2_launch_aes_encrypt(const uint8_t *key, uint32_t hashlen,
 	hipLaunchKernelGGL(aes_cbc_encrypt_kernel,
 	    dim3((unsigned)((n + AES_WG - 1) / AES_WG)), dim3(AES_WG), 0, s, a, k);
 	wipe(&k, sizeof(k));
+	return hipGetLastError();
+}
+
+hipError_t net2_launch_aes_tab_set(Net2CipherEnt *ents, uint32_t slot,
+    uint32_t side, const uint8_t *key, const uint8_t *alt_key, int no_cutoff,
+    uint32_t cutoff, uint32_t rx_start, hipStream_t s)
+{
+	if (ents == nullptr || (side != 0 && key == nullptr))
+		return hipErrorInvalidValue;
+	Net2CipherEnt nw = {};
+	if (side == NET2_AES_TAB_RX)
+		aes_tab_fill_rx(&nw, key, alt_key, no_cutoff != 0, cutoff, rx_start);
+	else if (side == NET2_AES_TAB_TX)
+		aes_tab_fill_tx(&nw, key);
+	hipLaunchKernelGGL(aes_tab_set_kernel, dim3(1), dim3(64), 0, s, ents + slot,
+	    side, nw);
+	wipe(&nw, sizeof(nw));
+	return hipGetLastError();
+}
+
+hipError_t net2_launch_aes_decrypt_mc(const AesTabArgs &kt, uint32_t hashlen,
+    const uint8_t *base, const uint64_t *offsets, const uint32_t *lens,
+    uint64_t n, const uint32_t *seq, const uint32_t *flags, const uint8_t *iv,
+    uint8_t *result, uint8_t *out, uint32_t *plen, hipStream_t s)
+{
+	if (n == 0)
+		return hipSuccess;
+	AesMcArgs m = {};
+	m.b.in = base;
+	m.b.out = out;
+	m.b.offsets = offsets;
+	m.b.lens = lens;
+	m.b.seq = seq;
+	m.b.flags = flags;
+	m.b.iv = iv;
+	m.b.result = result;
+	m.b.plen = plen;
+	m.b.n = n;
+	m.b.hashlen = hashlen;
+	m.conn = kt.conn;
+	m.tab = kt.tab;
+	m.slots = kt.slots;
+	hipLaunchKernelGGL(aes_cbc_decrypt_mc_kernel,
+	    dim3((unsigned)((n + AES_WG - 1) / AES_WG)), dim3(AES_WG), 0, s, m);
+	return hipGetLastError();
+}
+
+hipError_t net2_launch_aes_encrypt_mc(const AesTabArgs &kt, uint32_t hashlen,
+    const uint32_t *flags, const uint8_t *iv, uint8_t *base,
+    const uint64_t *offsets, const uint32_t *lens, const uint32_t *plen,
+    uint64_t n, uint8_t *result, uint32_t *wire_len, hipStream_t s)
+{
+	if (n == 0)
+		return hipSuccess;
+	AesMcArgs m = {};
+	m.b.out = base;
+	m.b.offsets = offsets;
+	m.b.lens = lens;
+	m.b.flags = flags;
+	m.b.iv = iv;
+	m.b.result = result;
+	m.b.plen = const_cast<uint32_t *>(plen);
+	m.b.wire_len = wire_len;
+	m.b.n = n;
+	m.b.hashlen = hashlen;
+	m.conn = kt.conn;
+	m.tab = kt.tab;
+	m.slots = kt.slots;
+	hipLaunchKernelGGL(aes_cbc_encrypt_mc_kernel,
+	    dim3((unsigned)((n + AES_WG - 1) / AES_WG)), dim3(AES_WG), 0, s, m);
 	return hipGetLastError();
 }

@@ -1,6 +1,6 @@
 /*
  * net2_dgram.cpp -- the calls on device-resident datagrams: HMAC sign /
- * verify and header IVs, the packet bursts, the payload cipher, the key table
+ * verify and header IVs, the packet bursts, the payload cipher, the key tables
  * and the bursts over many connections (include/net2/packet.h).  Argument
  * checks and launches in the caller's stream; nothing is staged here.
  */
@@ -473,14 +473,19 @@ struct net2_burst_keytab {
 namespace {
 
 /* Arguments first (by the caller), then: a usable device, and the table's. */
-int check_keytab_device(const struct net2_burst_keytab *tab)
+int check_table_device(int device)
 {
 	int cur = -1;
 	if (int rc = check_current_device())
 		return rc;
 	if (hipGetDevice(&cur) != hipSuccess)
 		return ENODEV;
-	return cur == tab->device ? 0 : EINVAL;
+	return cur == device ? 0 : EINVAL;
+}
+
+int check_keytab_device(const struct net2_burst_keytab *tab)
+{
+	return check_table_device(tab->device);
 }
 
 /* What the two _mc calls share: net2_packet_*_burst's checks with a table
@@ -647,5 +652,170 @@ NET2_EXPORT int net2_packet_encode_burst_mc(const struct net2_burst_keytab *tab,
 	    d_offsets, d_lens, n, (uint8_t *)d_base, burst_bins(n, w.bin),
 	    (hipStream_t)stream, NET2_HMAC_MODE_BURST_TX, tx));
 	FI_POINT(FI_KERNEL);
+	return 0;
+}
+
+/* ---- the cipher under per-connection keys: the device cipher-key table ---- */
+
+/*
+ * The cipher-key table of include/net2/packet.h: `slots` entries
+ * (Net2CipherEnt, aes_tab.h) in the memory of the device that was current
+ * when it was made.  Entries change only through the set / clear calls, each
+ * one launch in the caller's stream.
+ */
+struct net2_burst_ciphertab {
+	int device;
+	uint32_t slots;
+	Net2CipherEnt *ents;
+};
+
+NET2_EXPORT int net2_burst_ciphertab_create(int enc_alg, uint32_t slots,
+    struct net2_burst_ciphertab **tab)
+{
+	if (tab == nullptr)
+		return EINVAL;
+	*tab = nullptr;
+	if (enc_alg != NET2_ENC_AES256 || slots == 0)
+		return EINVAL;
+	if (int rc = check_current_device())
+		return rc;
+	std::unique_ptr<net2_burst_ciphertab> t(
+	    new (std::nothrow) net2_burst_ciphertab());
+	if (!t)
+		return ENOMEM;
+	if (hipGetDevice(&t->device) != hipSuccess)
+		return ENODEV;
+	t->slots = slots;
+	const size_t bytes = (size_t)slots * NET2_AES_TAB_ENT_BYTES;
+	HIP_TRY(hipMalloc((void **)&t->ents, bytes));
+	/* every slot unset before the first call that could read it, whatever
+	 * stream that call uses */
+	hipError_t e = hipMemset(t->ents, 0, bytes);
+	if (e == hipSuccess)
+		e = hipDeviceSynchronize();
+	if (e != hipSuccess) {
+		(void)hipFree(t->ents);
+		return hip_fail(e);
+	}
+	*tab = t.release();
+	return 0;
+}
+
+NET2_EXPORT void net2_burst_ciphertab_destroy(struct net2_burst_ciphertab *tab)
+{
+	if (tab == nullptr)
+		return;
+	/* the entries are cipher keys: none stays in freed device memory.  On
+	 * the table's device: wait for the work that may still read them, zero
+	 * them, free (hipFree waits for the memset). */
+	int prev = -1;
+	(void)hipGetDevice(&prev);
+	if (prev != tab->device)
+		(void)hipSetDevice(tab->device);
+	(void)hipDeviceSynchronize();
+	(void)hipMemset(tab->ents, 0, (size_t)tab->slots * NET2_AES_TAB_ENT_BYTES);
+	(void)hipFree(tab->ents);
+	if (prev >= 0 && prev != tab->device)
+		(void)hipSetDevice(prev);
+	delete tab;
+}
+
+NET2_EXPORT int net2_burst_ciphertab_set_rx(struct net2_burst_ciphertab *tab,
+    uint32_t slot, const struct net2_burst_rx_keys *keys,
+    const struct net2_burst_cipher_keys *ck, void *stream)
+{
+	if (tab == nullptr || keys == nullptr || slot >= tab->slots ||
+	    check_cipher_keys(ck) != 0)
+		return EINVAL;
+	if (keys->hash_alg != NET2_HASH_NIL && !hmac_row(keys->hash_alg))
+		return EINVAL;
+	/* as net2_packet_decrypt_burst: the alternate cipher key goes with
+	 * the alternate hash key */
+	const bool alt = keys->alt_hash_key != nullptr;
+	if (alt && (keys->hash_alg == NET2_HASH_NIL || ck->alt_enc_key == nullptr))
+		return EINVAL;
+	if (int rc = check_table_device(tab->device))
+		return rc;
+	HIP_TRY(net2_launch_aes_tab_set(tab->ents, slot, NET2_AES_TAB_RX,
+	    (const uint8_t *)ck->enc_key,
+	    alt ? (const uint8_t *)ck->alt_enc_key : nullptr, keys->alt_no_cutoff,
+	    keys->alt_cutoff, keys->rx_start, (hipStream_t)stream));
+	return 0;
+}
+
+NET2_EXPORT int net2_burst_ciphertab_set_tx(struct net2_burst_ciphertab *tab,
+    uint32_t slot, const struct net2_burst_cipher_keys *ck, void *stream)
+{
+	if (tab == nullptr || slot >= tab->slots || check_cipher_keys(ck) != 0)
+		return EINVAL;
+	if (int rc = check_table_device(tab->device))
+		return rc;
+	HIP_TRY(net2_launch_aes_tab_set(tab->ents, slot, NET2_AES_TAB_TX,
+	    (const uint8_t *)ck->enc_key, nullptr, 0, 0, 0, (hipStream_t)stream));
+	return 0;
+}
+
+NET2_EXPORT int net2_burst_ciphertab_clear(struct net2_burst_ciphertab *tab,
+    uint32_t slot, void *stream)
+{
+	if (tab == nullptr || slot >= tab->slots)
+		return EINVAL;
+	if (int rc = check_table_device(tab->device))
+		return rc;
+	HIP_TRY(net2_launch_aes_tab_set(tab->ents, slot, 0, nullptr, nullptr, 0, 0,
+	    0, (hipStream_t)stream));
+	return 0;
+}
+
+static bool digest_hashlen(uint32_t hashlen)
+{
+	return hashlen == 0 || hashlen == 32 || hashlen == 48 || hashlen == 64;
+}
+
+NET2_EXPORT int net2_packet_decrypt_burst_mc(
+    const struct net2_burst_ciphertab *tab, const uint32_t *d_conn,
+    uint32_t hashlen, const void *d_base, const uint64_t *d_offsets,
+    const uint32_t *d_lens, uint64_t n, const uint32_t *d_seq,
+    const uint32_t *d_flags, const void *d_iv, uint8_t *d_result, void *d_out,
+    uint32_t *d_plen, void *stream)
+{
+	if (tab == nullptr || !digest_hashlen(hashlen))
+		return EINVAL;
+	if (n == 0)
+		return 0;
+	/* any slot may have an alternate key, so d_seq is always needed */
+	if (!dgrams_ok(d_base, d_offsets, d_lens, n) || d_conn == nullptr ||
+	    d_seq == nullptr || d_flags == nullptr || d_iv == nullptr ||
+	    d_result == nullptr || d_out == nullptr || d_plen == nullptr)
+		return EINVAL;
+	if (int rc = check_table_device(tab->device))
+		return rc;
+	const AesTabArgs kt = { d_conn, tab->ents, tab->slots };
+	HIP_TRY(net2_launch_aes_decrypt_mc(kt, hashlen, (const uint8_t *)d_base,
+	    d_offsets, d_lens, n, d_seq, d_flags, (const uint8_t *)d_iv, d_result,
+	    (uint8_t *)d_out, d_plen, (hipStream_t)stream));
+	return 0;
+}
+
+NET2_EXPORT int net2_packet_encrypt_burst_mc(
+    const struct net2_burst_ciphertab *tab, const uint32_t *d_conn,
+    uint32_t hashlen, const uint32_t *d_flags, const void *d_iv, void *d_base,
+    const uint64_t *d_offsets, const uint32_t *d_lens, const uint32_t *d_plen,
+    uint64_t n, uint8_t *d_result, uint32_t *d_wire_len, void *stream)
+{
+	if (tab == nullptr || !digest_hashlen(hashlen))
+		return EINVAL;
+	if (n == 0)
+		return 0;
+	if (!dgrams_ok(d_base, d_offsets, d_lens, n) || d_conn == nullptr ||
+	    d_flags == nullptr || d_iv == nullptr || d_plen == nullptr ||
+	    d_result == nullptr || d_wire_len == nullptr)
+		return EINVAL;
+	if (int rc = check_table_device(tab->device))
+		return rc;
+	const AesTabArgs kt = { d_conn, tab->ents, tab->slots };
+	HIP_TRY(net2_launch_aes_encrypt_mc(kt, hashlen, d_flags,
+	    (const uint8_t *)d_iv, (uint8_t *)d_base, d_offsets, d_lens, d_plen, n,
+	    d_result, d_wire_len, (hipStream_t)stream));
 	return 0;
 }

@@ -324,6 +324,90 @@ int net2_packet_encode_burst_mc(const struct net2_burst_keytab *tab,
     uint64_t n, uint8_t *d_result, void *d_ws, size_t ws_bytes, void *stream);
 
 /*
+ * The payload cipher over many connections.  A net2_burst_ciphertab is to
+ * net2_packet_{decrypt,encrypt}_burst what a net2_burst_keytab is to the hash
+ * bursts: the cipher keys of many connections on the device, one slot per
+ * connection, so the encrypted datagrams of a shared socket's receive batch
+ * are decrypted in one call after net2_packet_decode_burst_mc authenticated
+ * them in one.  It is a table of its own (the cipher does not depend on the
+ * HMAC row; both tables are indexed by the same d_conn).  It lives in the
+ * memory of the device that is current when it is created, serves
+ * NET2_ENC_AES256, and every slot starts with neither side set.
+ *
+ *   net2_burst_ciphertab_set_rx  the slot's rx side from exactly the pair
+ *       net2_packet_decrypt_burst takes, under the same checks: ck->enc_key,
+ *       and ck->alt_enc_key when keys->alt_hash_key != NULL (an alternate key
+ *       is installed; then keys->hash_alg must not be 0).  Of `keys` only the
+ *       alternate-key state is stored: installed, alt_no_cutoff, alt_cutoff,
+ *       rx_start;
+ *   net2_burst_ciphertab_set_tx  its tx side: ck->enc_key, the key the
+ *       transmitter encrypts with (ck's alternate key is not used);
+ *   net2_burst_ciphertab_clear   both sides unset, the slot's keys zeroed.
+ *
+ * The round keys are expanded on the host inside the call and the new entry
+ * travels in the launch's arguments.  So, as for the key table: each call is
+ * asynchronous on `stream` and ordered with the bursts there, the keys need
+ * not outlive it, a slot set twice in a row ends with the second, and setting
+ * one side leaves the other as it is.  Work on other streams is not ordered
+ * with an update.  net2_burst_ciphertab_destroy waits for the table's device,
+ * zeroes the table there and frees it.
+ *
+ * 0, EINVAL (enc_alg not NET2_ENC_AES256, slots == 0, slot >= slots, a NULL
+ * argument, a key or alternate key that is not 32 bytes, keys->hash_alg
+ * neither 0 nor an HMAC row, the alternate-key mismatches of
+ * net2_packet_decrypt_burst, or -- checked last -- a calling thread whose
+ * current device is not the table's), ENOMEM, ENODEV or EIO.
+ */
+struct net2_burst_ciphertab;
+int net2_burst_ciphertab_create(int enc_alg, uint32_t slots,
+    struct net2_burst_ciphertab **tab);
+void net2_burst_ciphertab_destroy(struct net2_burst_ciphertab *tab);
+int net2_burst_ciphertab_set_rx(struct net2_burst_ciphertab *tab, uint32_t slot,
+    const struct net2_burst_rx_keys *keys,
+    const struct net2_burst_cipher_keys *ck, void *stream);
+int net2_burst_ciphertab_set_tx(struct net2_burst_ciphertab *tab, uint32_t slot,
+    const struct net2_burst_cipher_keys *ck, void *stream);
+int net2_burst_ciphertab_clear(struct net2_burst_ciphertab *tab, uint32_t slot,
+    void *stream);
+
+/*
+ * net2_packet_decrypt_burst / net2_packet_encrypt_burst with the keys of
+ * datagram i taken from slot d_conn[i] of `tab` (d_conn: n uint32 in device
+ * memory).  hashlen is one per call -- 0, 32, 48 or 64: a key table serves one
+ * HMAC row, so a _mc hash burst has one digest length.  d_seq is required on
+ * RX (any slot may have an alternate key).  Everything not stated here is the
+ * contract of the single-connection call, and for identical keys the outputs
+ * are those of the single-connection calls, bit for bit.
+ *   RX: a datagram whose incoming code is not NET2_PDECODE_OK keeps it
+ *   (NET2_PBURST_NOCONN from the hash step included), as does one without
+ *   PH_ENCRYPTED: d_plen[i] = 0, nothing written, no table look-up.  An OK
+ *   PH_ENCRYPTED datagram with d_conn[i] >= slots, or whose slot's rx side is
+ *   not set, becomes NET2_PBURST_NOCONN: d_plen[i] = 0, nothing written (the
+ *   reference would run its nil cipher there; the code tells the caller
+ *   which datagrams those are).  Otherwise it is decrypted under the slot's
+ *   active or alternate key, by net2_ck_rx_key's rule over the slot's own
+ *   state, d_seq[i] and d_flags[i] -- the choice the hash step made.
+ *   TX: a slot without PH_ENCRYPTED is treated as in the single call (no key,
+ *   no look-up).  The room check comes first: NET2_PENCODE_RESOURCE as there.
+ *   A PH_ENCRYPTED slot with room whose connection has no tx side is
+ *   NET2_PBURST_NOCONN, left untouched, d_wire_len[i] = 0.
+ * 0, EINVAL (tab NULL, hashlen not 0, 32, 48 or 64, a NULL pointer while
+ * n > 0 -- all before the device check -- or a calling thread whose device
+ * is not the table's), ENOMEM, ENODEV or EIO; n == 0 is 0 and launches
+ * nothing.
+ */
+int net2_packet_decrypt_burst_mc(const struct net2_burst_ciphertab *tab,
+    const uint32_t *d_conn, uint32_t hashlen, const void *d_base,
+    const uint64_t *d_offsets, const uint32_t *d_lens, uint64_t n,
+    const uint32_t *d_seq, const uint32_t *d_flags, const void *d_iv,
+    uint8_t *d_result, void *d_out, uint32_t *d_plen, void *stream);
+int net2_packet_encrypt_burst_mc(const struct net2_burst_ciphertab *tab,
+    const uint32_t *d_conn, uint32_t hashlen, const uint32_t *d_flags,
+    const void *d_iv, void *d_base, const uint64_t *d_offsets,
+    const uint32_t *d_lens, const uint32_t *d_plen, uint64_t n,
+    uint8_t *d_result, uint32_t *d_wire_len, void *stream);
+
+/*
  * Host-memory bursts: the same hash steps for datagrams that live in host
  * memory -- the reference's case: each received one is a net2_buffer filled
  * by net2_sockdgram_recv (src/sockdgram.c:67-108) and decoded at
