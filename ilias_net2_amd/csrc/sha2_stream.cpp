@@ -11,7 +11,7 @@
  * committed only after the request succeeds.
  */
 #include "sha2_coalesce.h"
-#include "sha2_device.h"
+#include "sha2_consts.h"
 
 #include "../../include/net2/sha2.h"
 
