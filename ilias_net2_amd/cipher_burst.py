@@ -27,6 +27,22 @@ KEYLEN = 32         # AES-256
 IVLEN = 16
 
 
+def limits(wave_max: int) -> None:
+    """``net2_aes_burst_limits``: the largest burst that ``decrypt_burst`` and
+    ``decrypt_burst_mc`` decrypt one wave per datagram (0: never; < 0: the
+    default).  Process-wide; results do not depend on it, only the time."""
+    check(_lib.lib().net2_aes_burst_limits(wave_max), "net2_aes_burst_limits")
+
+
+def stats() -> dict:
+    """``net2_aes_burst_stats``: this process's decrypt launches so far, by
+    form: ``{"lane_launches": ..., "wave_launches": ...}``."""
+    lane, wave = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    check(_lib.lib().net2_aes_burst_stats(ctypes.byref(lane), ctypes.byref(wave)),
+          "net2_aes_burst_stats")
+    return {"lane_launches": lane.value, "wave_launches": wave.value}
+
+
 def _cipher_keys(key: bytes, alt_key: Optional[bytes]):
     """struct net2_burst_cipher_keys and the buffers it points into."""
     kb = ctypes.create_string_buffer(bytes(key), max(len(key), 1))

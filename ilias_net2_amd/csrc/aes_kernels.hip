@@ -7,7 +7,8 @@
  *
  * One lane per datagram, as in the hash bursts: on TX the CBC chain is serial
  * within a datagram anyway, and RX takes the same shape so both directions
- * share the block code (aes_device.h) and the tests.
+ * share the block code (aes_device.h) and the tests.  Small RX bursts take
+ * the wave form instead (one wave per datagram, further down).
  *
  * LDS layout.  A workgroup is 256 lanes and holds one T-table (Te0 forward,
  * Td0 inverse) replicated 32 times: entry x for lane l is dword
@@ -37,6 +38,7 @@
 #include "aes_launch.h"
 #include "aes_sched.h"
 #include "aes_tab.h"
+#include "aes_wave.h"
 
 #include <stddef.h>
 #include <string.h>
@@ -615,6 +617,197 @@ __global__ __launch_bounds__(AES_WG) void aes_cbc_encrypt_mc_kernel(
 }
 
 /*
+ * The wave form of RX, for small bursts (net2_aes_burst_limits): one wave per
+ * datagram, the lanes taking the datagram's blocks 64 to a pass -- CBC
+ * decryption has no serial chain, block b needs ciphertext blocks b and b - 1
+ * only.  With one lane per datagram a burst of a few thousand datagrams is
+ * at most one wave per SIMD and lasts as long as its longest lane, 89 blocks
+ * one after the other for a 1,424-byte ciphertext; here that datagram is two
+ * passes.  aes_wave.h has the schedule (which block a lane takes in a pass,
+ * the order of the passes, a block's prev, when the padding verdict is taken)
+ * and why that order is safe in place; this kernel follows it call by call.
+ *
+ * A workgroup is AES_WAVES waves and builds the one table the lane form
+ * builds, lane l of a wave on bank l & 31: a ds_read_b32 is served per
+ * half-wave of 32 lanes over 32 banks and every lane of a half-wave reads its
+ * own bank, so here too no lookup conflicts and the time of a lookup does
+ * not depend on key or data.  Idle lanes of a pass (blocks past the end) run
+ * the rounds on zeros rather than branch around them.  The table build ends
+ * in the kernel's only barrier and comes before anything that can end a
+ * wave: waves without a datagram or without cipher work reach it like the
+ * others.  Wave w of workgroup g takes datagrams (g * per_wave + k) *
+ * AES_WAVES + w, k = 0 .. per_wave - 1: the launch raises per_wave with n so
+ * that a larger burst builds fewer tables.
+ *
+ * What is per datagram is per wave, so wave-uniform: the index (readfirstlane
+ * of the wave number, which lets the compiler keep offsets, lengths and flags
+ * in scalar registers), the prep step (lane 0 runs the lane form's
+ * decrypt_prep / decrypt_mc_prep, the block count is broadcast) and the key
+ * choice.  The three key sources share the body: one key in the launch's
+ * arguments, read from there (KS_ONE); the active and the alternate key in
+ * the arguments, both copied to LDS as in the lane form and the wave's pick
+ * by aes_rx_alt moved to scalar registers (KS_ALT); the cipher-key table,
+ * the datagram's entry looked up as in the _mc lane form and the picked
+ * schedule moved to scalar registers (KS_TAB).
+ *
+ * A lane touches only whole blocks of its datagram's payload, with the
+ * lane form's 16-byte accesses at byte alignment and 64-bit offsets.
+ */
+constexpr int AES_WAVES = AES_WG / 64;	/* datagrams per workgroup and step */
+enum { KS_ONE = 0, KS_ALT = 1, KS_TAB = 2 };
+
+template <int KS> struct AesWaveArgs;
+template <> struct AesWaveArgs<KS_ONE> {
+	AesBurstArgs b;
+	AesKeys<1> keys;
+	__device__ __forceinline__ const AesBurstArgs &burst() const { return b; }
+};
+template <> struct AesWaveArgs<KS_ALT> {
+	AesBurstArgs b;
+	AesKeys<2> keys;
+	__device__ __forceinline__ const AesBurstArgs &burst() const { return b; }
+};
+template <> struct AesWaveArgs<KS_TAB> {
+	AesMcArgs m;
+	__device__ __forceinline__ const AesBurstArgs &burst() const { return m.b; }
+};
+
+/* A schedule every lane of the wave shares, out of LDS or out of a table
+ * entry (16-byte aligned either way), held in scalar registers. */
+struct RkWave {
+	uint32_t w[NET2_AES_RKWORDS];
+	__device__ __forceinline__ explicit RkWave(const uint32_t *p)
+	{
+		const u32x4 *q = reinterpret_cast<const u32x4 *>(p);
+#pragma unroll
+		for (int k = 0; k < NET2_AES_RKWORDS / 4; k++) {
+			const u32x4 v = q[k];
+			w[4 * k] = __builtin_amdgcn_readfirstlane(v.x);
+			w[4 * k + 1] = __builtin_amdgcn_readfirstlane(v.y);
+			w[4 * k + 2] = __builtin_amdgcn_readfirstlane(v.z);
+			w[4 * k + 3] = __builtin_amdgcn_readfirstlane(v.w);
+		}
+	}
+	__device__ __forceinline__ uint32_t operator()(int i) const
+	{
+		return w[i];
+	}
+};
+
+/*
+ * Datagram i, nb >= 1 blocks, by the calling wave (every lane calls; i, nb,
+ * fl and the key are wave-uniform).  The passes of aes_wave.h, last pass
+ * first.  In every run a lane loads its block and its prev, decrypts, and
+ * stores: its store data depends on both loads, and the wave runs in
+ * lockstep, so within a run all loads are done before the first store; the
+ * runs before it stored to later passes' blocks only.  So in place every
+ * ciphertext block is in registers before a store can overwrite it.  The
+ * padding verdict falls in the first run, before the datagram's first store:
+ * a BAD datagram is never written.
+ */
+template <class K>
+__device__ __forceinline__ void decrypt_by_wave(const AesBurstArgs &a,
+    uint64_t i, uint32_t nb, uint32_t fl, const LdsTab &T, const K &rk,
+    uint32_t lane)
+{
+	const uint64_t off = a.offsets[i] + payload_at(fl, a.hashlen);
+	const uint8_t *src = a.in + off;
+	uint8_t *dst = a.out + off;
+	const uint32_t runs = aes_wave_passes(nb);
+	uint32_t pad = 0;
+
+	for (uint32_t r = 0; r < runs; r++) {
+		const uint32_t b = aes_wave_block(aes_wave_pass_of_run(nb, r), lane);
+		const bool mine = b < nb;
+		uint32_t x[4] = { 0, 0, 0, 0 }, prev[4] = { 0, 0, 0, 0 };
+		if (mine) {
+			ld16(src + 16 * (uint64_t)b, x);
+			if (aes_wave_prev_is_iv(b))
+				ld16(a.iv + NET2_AES_BLOCK * i, prev);
+			else
+				ld16(src + 16 * (uint64_t)aes_wave_prev(b), prev);
+		}
+		aes_block<true>(T, rk, x);
+#pragma unroll
+		for (int k = 0; k < 4; k++)
+			x[k] ^= prev[k];
+		if (r == NET2_AES_WAVE_VERDICT_RUN) {
+			/* the last block's lane tells the wave */
+			pad = __builtin_amdgcn_readlane(aes_pkcs7_pad(x),
+			    aes_wave_verdict_lane(nb));
+			if (pad == 0)
+				break;
+		}
+		if (mine)
+			st16(dst + 16 * (uint64_t)b, x);
+	}
+	if (lane == 0) {
+		if (pad == 0)
+			a.result[i] = PKT_BAD;
+		a.plen[i] = pad != 0 ? 16 * nb - pad : 0u;
+	}
+}
+
+template <int KS>
+__global__ __launch_bounds__(AES_WG) void aes_cbc_decrypt_wave_kernel(
+    const AesWaveArgs<KS> w, const uint32_t per_wave)
+{
+	__shared__ uint32_t tab[256 * AES_REP];
+	__shared__ __attribute__((aligned(16))) uint32_t
+	    rks[KS == KS_ALT ? 2 * AES_RK_STRIDE : 4];
+
+	const AesBurstArgs &a = w.burst();
+	const uint32_t t = threadIdx.x;
+	if constexpr (KS == KS_ALT) {
+		if (t < NET2_AES_RKWORDS)
+			rks[t] = w.keys.k[0].w[t];
+		else if (t >= 64 && t < 64 + NET2_AES_RKWORDS)
+			rks[AES_RK_STRIDE + t - 64] = w.keys.k[1].w[t - 64];
+	}
+	/* the one barrier (it publishes rks as well): before any wave can end */
+	aes_build_table<true>(tab);
+
+	const uint32_t lane = t & 63u;
+	const uint32_t wv = __builtin_amdgcn_readfirstlane(t >> 6);
+	const LdsTab T = { tab + (t & (AES_REP - 1)) };
+	for (uint32_t k = 0; k < per_wave; k++) {
+		const uint64_t i = ((uint64_t)blockIdx.x * per_wave + k) * AES_WAVES + wv;
+		if (i >= a.n)
+			break;
+		/* lane 0 settles what needs no cipher, as a lane of the lane form */
+		uint32_t nb = 0;
+		if (lane == 0) {
+			if constexpr (KS == KS_TAB)
+				nb = decrypt_mc_prep(w.m, i);
+			else
+				nb = decrypt_prep(a, i);
+		}
+		nb = __builtin_amdgcn_readfirstlane(nb);
+		if (nb == 0)
+			continue;
+		const uint32_t fl = a.flags[i];
+		if constexpr (KS == KS_ONE) {
+			const RkArgs K = { w.keys.k[0] };
+			decrypt_by_wave(a, i, nb, fl, T, K, lane);
+		} else if constexpr (KS == KS_ALT) {
+			/* net2_ck_rx_key, as the HMAC step chose */
+			const bool alt = aes_rx_alt(true, a.no_cutoff != 0, fl, a.seq[i],
+			    a.cutoff, a.rx_start);
+			const RkWave K(rks + (alt ? AES_RK_STRIDE : 0));
+			decrypt_by_wave(a, i, nb, fl, T, K, lane);
+		} else {
+			bool in;
+			const Net2CipherEnt *e = ciphertab_ent(w.m, i, &in);
+			const u32x4 mt = *reinterpret_cast<const u32x4 *>(e->meta);
+			const bool alt = aes_rx_alt((mt.x & NET2_CT_RX_ALT) != 0,
+			    (mt.x & NET2_CT_RX_NOCUT) != 0, fl, a.seq[i], mt.y, mt.z);
+			const RkWave K(e->dec[alt ? 1 : 0]);
+			decrypt_by_wave(a, i, nb, fl, T, K, lane);
+		}
+	}
+}
+
+/*
  * One slot's update (net2_burst_ciphertab_set_rx / _set_tx / _clear): the new
  * entry arrives by value and one wave stores it, 16 bytes per lane (the
  * argument is read with constant indices only and selected per lane: a
@@ -784,6 +977,106 @@ hipError_t net2_launch_aes_decrypt_mc(const AesTabArgs &kt, uint32_t hashlen,
 	m.slots = kt.slots;
 	hipLaunchKernelGGL(aes_cbc_decrypt_mc_kernel,
 	    dim3((unsigned)((n + AES_WG - 1) / AES_WG)), dim3(AES_WG), 0, s, m);
+	return hipGetLastError();
+}
+
+/* ---- the wave form of the decrypt launches ---------------------------------- */
+
+namespace {
+
+/*
+ * Datagrams per wave (the kernel's per_wave) and the grid for a burst of n:
+ * one datagram per wave until the grid would pass AES_WAVE_GRID workgroups
+ * (five of them, 32 KiB of table each, are resident per CU of an MI355X's
+ * 256), then as many as keep it there, 16 at the most.
+ */
+constexpr uint64_t AES_WAVE_GRID = 1280;
+constexpr uint64_t AES_WAVE_PER_MAX = 16;
+
+uint32_t wave_per(uint64_t n)
+{
+	const uint64_t per = (n + AES_WAVES * AES_WAVE_GRID - 1) /
+	    (AES_WAVES * AES_WAVE_GRID);
+	return (uint32_t)(per < 1 ? 1 : per > AES_WAVE_PER_MAX ? AES_WAVE_PER_MAX : per);
+}
+
+dim3 wave_grid(uint64_t n, uint32_t per)
+{
+	const uint64_t step = (uint64_t)AES_WAVES * per;
+	return dim3((unsigned)((n + step - 1) / step));
+}
+
+}	/* namespace */
+
+hipError_t net2_launch_aes_decrypt_wave(const uint8_t *key, const AesRxAlt &alt,
+    uint32_t hashlen, const uint8_t *base, const uint64_t *offsets,
+    const uint32_t *lens, uint64_t n, const uint32_t *seq,
+    const uint32_t *flags, const uint8_t *iv, uint8_t *result, uint8_t *out,
+    uint32_t *plen, hipStream_t s)
+{
+	if (n == 0)
+		return hipSuccess;
+	AesBurstArgs a = {};
+	a.in = base;
+	a.out = out;
+	a.offsets = offsets;
+	a.lens = lens;
+	a.seq = seq;
+	a.flags = flags;
+	a.iv = iv;
+	a.result = result;
+	a.plen = plen;
+	a.n = n;
+	a.hashlen = hashlen;
+	a.no_cutoff = alt.no_cutoff != 0;
+	a.cutoff = alt.cutoff;
+	a.rx_start = alt.rx_start;
+	const uint32_t per = wave_per(n);
+	if (alt.alt_key != nullptr) {
+		AesWaveArgs<KS_ALT> w;
+		w.b = a;
+		aes256_dec_schedule(key, &w.keys.k[0]);
+		aes256_dec_schedule(alt.alt_key, &w.keys.k[1]);
+		hipLaunchKernelGGL(aes_cbc_decrypt_wave_kernel<KS_ALT>, wave_grid(n, per),
+		    dim3(AES_WG), 0, s, w, per);
+		wipe(&w.keys, sizeof(w.keys));
+	} else {
+		AesWaveArgs<KS_ONE> w;
+		w.b = a;
+		aes256_dec_schedule(key, &w.keys.k[0]);
+		hipLaunchKernelGGL(aes_cbc_decrypt_wave_kernel<KS_ONE>, wave_grid(n, per),
+		    dim3(AES_WG), 0, s, w, per);
+		wipe(&w.keys, sizeof(w.keys));
+	}
+	return hipGetLastError();
+}
+
+hipError_t net2_launch_aes_decrypt_mc_wave(const AesTabArgs &kt,
+    uint32_t hashlen, const uint8_t *base, const uint64_t *offsets,
+    const uint32_t *lens, uint64_t n, const uint32_t *seq,
+    const uint32_t *flags, const uint8_t *iv, uint8_t *result, uint8_t *out,
+    uint32_t *plen, hipStream_t s)
+{
+	if (n == 0)
+		return hipSuccess;
+	AesWaveArgs<KS_TAB> w = {};
+	w.m.b.in = base;
+	w.m.b.out = out;
+	w.m.b.offsets = offsets;
+	w.m.b.lens = lens;
+	w.m.b.seq = seq;
+	w.m.b.flags = flags;
+	w.m.b.iv = iv;
+	w.m.b.result = result;
+	w.m.b.plen = plen;
+	w.m.b.n = n;
+	w.m.b.hashlen = hashlen;
+	w.m.conn = kt.conn;
+	w.m.tab = kt.tab;
+	w.m.slots = kt.slots;
+	const uint32_t per = wave_per(n);
+	hipLaunchKernelGGL(aes_cbc_decrypt_wave_kernel<KS_TAB>, wave_grid(n, per),
+	    dim3(AES_WG), 0, s, w, per);
 	return hipGetLastError();
 }
 

@@ -78,4 +78,21 @@ hipError_t net2_launch_aes_encrypt_mc(const AesTabArgs &kt, uint32_t hashlen,
     const uint64_t *offsets, const uint32_t *lens, const uint32_t *plen,
     uint64_t n, uint8_t *result, uint32_t *wire_len, hipStream_t s);
 
+/*
+ * The wave form of the two decrypt launches, for small bursts: one wave per
+ * datagram, its blocks spread over the lanes (aes_wave.h), in place of one
+ * lane per datagram.  Same arguments, same codes, lengths and output bytes;
+ * which form a call takes is net2_dgram.cpp's choice (net2_aes_burst_limits).
+ */
+hipError_t net2_launch_aes_decrypt_wave(const uint8_t *key, const AesRxAlt &alt,
+    uint32_t hashlen, const uint8_t *base, const uint64_t *offsets,
+    const uint32_t *lens, uint64_t n, const uint32_t *seq,
+    const uint32_t *flags, const uint8_t *iv, uint8_t *result, uint8_t *out,
+    uint32_t *plen, hipStream_t s);
+hipError_t net2_launch_aes_decrypt_mc_wave(const AesTabArgs &kt,
+    uint32_t hashlen, const uint8_t *base, const uint64_t *offsets,
+    const uint32_t *lens, uint64_t n, const uint32_t *seq,
+    const uint32_t *flags, const uint8_t *iv, uint8_t *result, uint8_t *out,
+    uint32_t *plen, hipStream_t s);
+
 #endif /* NET2_AES_LAUNCH_H */

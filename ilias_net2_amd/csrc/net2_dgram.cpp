@@ -398,6 +398,63 @@ NET2_EXPORT int net2_packet_encode_burst(int hash_alg, const void *hash_key,
 
 /* ---- the payload cipher of the bursts (aes_kernels.hip) -------------------- */
 
+namespace {
+
+/*
+ * The largest burst decrypted in the wave form (one wave per datagram): the
+ * measured crossover of tools/aes_burst_sizes.py (DESIGN.md 5.5.5,
+ * profiles/aes_burst_wave/sizes.jsonl): the largest measured size at which,
+ * as at every smaller one, the wave form beat the lane form by more than the
+ * lane form's own spread (209 against 283 us there; at 262,144 datagrams one
+ * lane per datagram fills the device and wins, 493 against 683 us).
+ */
+constexpr int64_t AES_WAVE_MAX_DEFAULT = 65536;
+
+/* net2_aes_burst_limits' setting (-1: none) and net2_aes_burst_stats' counts */
+std::atomic<int64_t> g_aes_wave_max{-1};
+std::atomic<uint64_t> g_aes_lane_launches{0}, g_aes_wave_launches{0};
+
+/* Whether a decrypt burst of n takes the wave form: the setting, else
+ * NET2_AES_WAVE_MAX from the environment at first use, else the default. */
+bool aes_wave_form(uint64_t n)
+{
+	int64_t max_n = g_aes_wave_max.load(std::memory_order_relaxed);
+	if (max_n < 0) {
+		static const int64_t env = [] {
+			const char *e = getenv("NET2_AES_WAVE_MAX");
+			return e != nullptr && *e != '\0' ?
+			    (int64_t)(strtoull(e, nullptr, 10) & INT64_MAX) :
+			    AES_WAVE_MAX_DEFAULT;
+		}();
+		max_n = env;
+	}
+	return n <= (uint64_t)max_n;
+}
+
+void aes_count_launch(bool wave)
+{
+	(wave ? g_aes_wave_launches : g_aes_lane_launches)
+	    .fetch_add(1, std::memory_order_relaxed);
+}
+
+}	/* namespace */
+
+NET2_EXPORT int net2_aes_burst_limits(int64_t wave_max)
+{
+	g_aes_wave_max.store(wave_max < 0 ? -1 : wave_max, std::memory_order_relaxed);
+	return 0;
+}
+
+NET2_EXPORT int net2_aes_burst_stats(uint64_t *lane_launches,
+    uint64_t *wave_launches)
+{
+	if (lane_launches != nullptr)
+		*lane_launches = g_aes_lane_launches.load(std::memory_order_relaxed);
+	if (wave_launches != nullptr)
+		*wave_launches = g_aes_wave_launches.load(std::memory_order_relaxed);
+	return 0;
+}
+
 NET2_EXPORT int net2_packet_decrypt_burst(const struct net2_burst_rx_keys *k,
     const struct net2_burst_cipher_keys *ck, const void *d_base,
     const uint64_t *d_offsets, const uint32_t *d_lens, uint64_t n,
@@ -423,11 +480,15 @@ NET2_EXPORT int net2_packet_decrypt_burst(const struct net2_burst_rx_keys *k,
 		return rc;
 	const AesRxAlt ra = { alt ? (const uint8_t *)ck->alt_enc_key : nullptr,
 	    k->alt_no_cutoff, k->alt_cutoff, k->rx_start };
-	HIP_TRY(net2_launch_aes_decrypt((const uint8_t *)ck->enc_key, ra,
+	/* a small burst: one wave per datagram (results are the same) */
+	const bool wave = aes_wave_form(n);
+	HIP_TRY((wave ? net2_launch_aes_decrypt_wave : net2_launch_aes_decrypt)(
+	    (const uint8_t *)ck->enc_key, ra,
 	    k->hash_alg != NET2_HASH_NIL ? (uint32_t)digest_len(k->hash_alg) : 0,
 	    (const uint8_t *)d_base, d_offsets, d_lens, n, d_seq, d_flags,
 	    (const uint8_t *)d_iv, d_result, (uint8_t *)d_out, d_plen,
 	    (hipStream_t)stream));
+	aes_count_launch(wave);
 	return 0;
 }
 
@@ -791,9 +852,12 @@ NET2_EXPORT int net2_packet_decrypt_burst_mc(
 	if (int rc = check_table_device(tab->device))
 		return rc;
 	const AesTabArgs kt = { d_conn, tab->ents, tab->slots };
-	HIP_TRY(net2_launch_aes_decrypt_mc(kt, hashlen, (const uint8_t *)d_base,
-	    d_offsets, d_lens, n, d_seq, d_flags, (const uint8_t *)d_iv, d_result,
-	    (uint8_t *)d_out, d_plen, (hipStream_t)stream));
+	const bool wave = aes_wave_form(n);
+	HIP_TRY((wave ? net2_launch_aes_decrypt_mc_wave : net2_launch_aes_decrypt_mc)(
+	    kt, hashlen, (const uint8_t *)d_base, d_offsets, d_lens, n, d_seq,
+	    d_flags, (const uint8_t *)d_iv, d_result, (uint8_t *)d_out, d_plen,
+	    (hipStream_t)stream));
+	aes_count_launch(wave);
 	return 0;
 }
 

@@ -238,6 +238,26 @@ int net2_packet_encrypt_burst(const struct net2_burst_cipher_keys *ck,
     uint32_t *d_wire_len, void *stream);
 
 /*
+ * Size threshold of the decrypt bursts, process-wide (diagnostics, tests and
+ * A/B runs), for net2_packet_decrypt_burst and net2_packet_decrypt_burst_mc
+ * alike: wave_max is the largest burst decrypted one wave per datagram, the
+ * datagram's blocks spread over the wave's lanes (0: never); a larger burst
+ * is decrypted one lane per datagram.  A value < 0 restores the default (the
+ * measured crossover, 65,536 datagrams on an MI355X, or NET2_AES_WAVE_MAX
+ * when set in the environment at first use).  Results do not depend on it --
+ * codes, lengths and every output byte are the same in both forms -- only the
+ * time does.  The encrypt bursts have one form.  Always 0; needs no device.
+ */
+int net2_aes_burst_limits(int64_t wave_max);
+
+/*
+ * Decrypt launches of this process so far, by form (either pointer may be
+ * NULL): the only way to tell which form a call took.  A call with n == 0
+ * or one refused by its argument checks launches nothing.  Always 0.
+ */
+int net2_aes_burst_stats(uint64_t *lane_launches, uint64_t *wave_launches);
+
+/*
  * Keyed bursts over many connections.  The reference terminates many
  * connections on one UDP socket (src/udp_connection.c:81-170: net2_conn_p2p
  * keyed by remote address under one net2_udpsocket), so what a receive loop
