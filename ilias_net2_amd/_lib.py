@@ -90,6 +90,8 @@ SIGNATURES = {
                                                  ctypes.c_void_p]),
     "net2_sha2_bin_limits": (ctypes.c_int, [ctypes.c_uint32, ctypes.c_int64]),
     "net2_sha2_burst_limits": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64]),
+    # keyed hash-burst launches by form (lane, wave)
+    "net2_sha2_burst_stats": (ctypes.c_int, [_c_u64p, _c_u64p]),
     "net2_sha2_batch": (ctypes.c_int, [
         ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
         ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_void_p,

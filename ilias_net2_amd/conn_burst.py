@@ -117,6 +117,16 @@ def burst_workspace(n: int, device, stream=None):
     return ws
 
 
+def burst_stats():
+    """``net2_sha2_burst_stats``: this process's keyed hash-burst launches so
+    far as ``(lane, wave)`` -- one datagram per lane, or the one-launch
+    small-burst form.  Host state; needs no device."""
+    lane, wave = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    check(_lib.lib().net2_sha2_burst_stats(ctypes.byref(lane), ctypes.byref(wave)),
+          "net2_sha2_burst_stats")
+    return lane.value, wave.value
+
+
 def _burst_args(data, conn, offsets, lens):
     import torch
     _need(data, torch.uint8, "data")

@@ -202,6 +202,15 @@ uint32_t *burst_bins(uint64_t n, uint32_t *bin)
 	return n >= (uint64_t)min_n ? bin : nullptr;
 }
 
+/* net2_sha2_burst_stats' counts: keyed hash-burst launches by form */
+std::atomic<uint64_t> g_burst_lane_launches{0}, g_burst_wave_launches{0};
+
+void burst_count_launch(bool wave)
+{
+	(wave ? g_burst_wave_launches : g_burst_lane_launches)
+	    .fetch_add(1, std::memory_order_relaxed);
+}
+
 }	/* namespace */
 
 /*
@@ -253,6 +262,7 @@ int decode_burst(const struct net2_burst_rx_keys *k, uint32_t ivlen,
 			    d_result, enc_set ? (uint8_t *)d_iv : nullptr,
 			    enc_set ? ivlen : 0, nullptr, NET2_HMAC_MODE_BURST_RX,
 			    s));
+			burst_count_launch(true);
 			FI_POINT(FI_KERNEL);
 			return 0;
 		}
@@ -260,6 +270,7 @@ int decode_burst(const struct net2_burst_rx_keys *k, uint32_t ivlen,
 		    k->hash_keylen, (const uint8_t *)d_base, d_offsets, d_lens, 0,
 		    0, n, w.verdict, burst_bins(n, w.bin), s,
 		    NET2_HMAC_MODE_BURST_RX, &rx));
+		burst_count_launch(false);
 	} else {
 		HIP_TRY(net2_launch_burst_prep((uint8_t *)d_base, d_offsets,
 		    d_lens, n, 0, 0, enc_set, 0, nullptr, nullptr, seq,
@@ -307,6 +318,7 @@ int encode_burst(int hash_alg, const void *hash_key, size_t hash_keylen,
 			    (const uint8_t *)hash_key, hash_keylen,
 			    (const uint8_t *)d_base, d_offsets, d_lens, n, &tx,
 			    d_result, nullptr, 0, out, NET2_HMAC_MODE_BURST_TX, s));
+			burst_count_launch(true);
 			FI_POINT(FI_KERNEL);
 			return 0;
 		}
@@ -314,6 +326,7 @@ int encode_burst(int hash_alg, const void *hash_key, size_t hash_keylen,
 		    hash_keylen, (const uint8_t *)d_base, d_offsets, d_lens, 0,
 		    0, n, out, bin ? burst_bins(n, w.bin) : nullptr, s,
 		    NET2_HMAC_MODE_BURST_TX, &tx));
+		burst_count_launch(false);
 		FI_POINT(FI_KERNEL);
 		return 0;
 	}
@@ -335,6 +348,16 @@ NET2_EXPORT int net2_sha2_burst_limits(int64_t wave_max, int64_t bin_min)
 {
 	net2_set_burst_wave_max(wave_max);
 	g_burst_bin_min.store(bin_min < 0 ? -1 : bin_min, std::memory_order_relaxed);
+	return 0;
+}
+
+NET2_EXPORT int net2_sha2_burst_stats(uint64_t *lane_launches,
+    uint64_t *wave_launches)
+{
+	if (lane_launches != nullptr)
+		*lane_launches = g_burst_lane_launches.load(std::memory_order_relaxed);
+	if (wave_launches != nullptr)
+		*wave_launches = g_burst_wave_launches.load(std::memory_order_relaxed);
 	return 0;
 }
 
@@ -672,6 +695,20 @@ NET2_EXPORT int net2_packet_decode_burst_mc(const struct net2_burst_keytab *tab,
 	if (rc != 0 || n == 0)
 		return rc;
 	hipStream_t s = (hipStream_t)stream;
+	const KeyTabArgs kt = { d_conn, tab->ents, tab->slots };
+	if (n <= net2_burst_wave_max()) {
+		/* a small burst: 1 to 16 datagrams per workgroup; codes, headers
+		 * and IVs stored by that one launch, the workspace not touched */
+		BurstArgs rx = {};
+		rx.seq = d_seq;
+		rx.flags = d_flags;
+		HIP_TRY(net2_launch_burst_wave_mc(tab->hash_alg, kt,
+		    (const uint8_t *)d_base, d_offsets, d_lens, n, rx, d_result,
+		    (uint8_t *)d_iv, ivlen, nullptr, NET2_HMAC_MODE_BURST_RX, s));
+		burst_count_launch(true);
+		FI_POINT(FI_KERNEL);
+		return 0;
+	}
 	BurstWs w;
 	burst_layout(n, (uint8_t *)d_ws, &w);
 	/* as decode_burst's keyed lane form: the HMAC kernel decodes the
@@ -680,10 +717,10 @@ NET2_EXPORT int net2_packet_decode_burst_mc(const struct net2_burst_keytab *tab,
 	rx.seq = d_seq != nullptr ? d_seq : w.seq;
 	rx.flags = d_flags != nullptr ? d_flags : w.flags;
 	rx.status = w.status;
-	const KeyTabArgs kt = { d_conn, tab->ents, tab->slots };
 	HIP_TRY(net2_launch_hmac_mc(tab->hash_alg, kt, (const uint8_t *)d_base,
 	    d_offsets, d_lens, n, w.verdict, burst_bins(n, w.bin), s,
 	    NET2_HMAC_MODE_BURST_RX, rx));
+	burst_count_launch(false);
 	FI_POINT(FI_KERNEL);
 	/* ... and the final kernel folds the verdicts in and derives the IV
 	 * of every OK PH_ENCRYPTED datagram whose connection has a cipher key
@@ -702,16 +739,27 @@ NET2_EXPORT int net2_packet_encode_burst_mc(const struct net2_burst_keytab *tab,
 	    d_result, d_ws, ws_bytes, d_seq != nullptr && d_flags != nullptr);
 	if (rc != 0 || n == 0)
 		return rc;
-	BurstWs w;
-	burst_layout(n, (uint8_t *)d_ws, &w);
 	BurstArgs tx = {};
 	tx.seq = const_cast<uint32_t *>(d_seq);
 	tx.flags = const_cast<uint32_t *>(d_flags);
 	tx.status = d_result;		/* the TX code is final in the kernel */
 	const KeyTabArgs kt = { d_conn, tab->ents, tab->slots };
+	if (n <= net2_burst_wave_max()) {
+		/* a small burst: 1 to 16 datagrams per workgroup */
+		HIP_TRY(net2_launch_burst_wave_mc(tab->hash_alg, kt,
+		    (const uint8_t *)d_base, d_offsets, d_lens, n, tx, d_result,
+		    nullptr, 0, (uint8_t *)d_base, NET2_HMAC_MODE_BURST_TX,
+		    (hipStream_t)stream));
+		burst_count_launch(true);
+		FI_POINT(FI_KERNEL);
+		return 0;
+	}
+	BurstWs w;
+	burst_layout(n, (uint8_t *)d_ws, &w);
 	HIP_TRY(net2_launch_hmac_mc(tab->hash_alg, kt, (const uint8_t *)d_base,
 	    d_offsets, d_lens, n, (uint8_t *)d_base, burst_bins(n, w.bin),
 	    (hipStream_t)stream, NET2_HMAC_MODE_BURST_TX, tx));
+	burst_count_launch(false);
 	FI_POINT(FI_KERNEL);
 	return 0;
 }

@@ -2283,6 +2283,239 @@ __global__ __launch_bounds__(128) void burst_wave_kernel(
 	result[i] = (uint8_t)g.st;
 }
 
+/*
+ * burst_wave_kernel's sibling for bursts over many connections
+ * (net2_packet_{decode,encode}_burst_mc at most net2_burst_wave_max()
+ * datagrams): the same two waves, G datagrams, K + W rows and passes, with
+ * the keys of datagram i taken from entry conn[i] of the device key table as
+ * hmac_mc_kernel's lanes take them -- no key in the arguments, none in LDS.
+ * A body of its own, not a shared template: the single-connection instances
+ * keep their instruction schedules.
+ *
+ * The 64 / G replica lanes of a datagram read the same conn[i], meta words
+ * and midstates (one request per distinct address).  The entry's address is
+ * held in two VGPRs across the pass loop: at two waves per SIMD there are
+ * registers to spare, so the outer midstate is loaded from it where the outer
+ * block needs it, without hmac_item's second look-up.  A lane with i >= n
+ * reads neither conn nor the table.  Codes, headers, IVs and sealed fields are
+ * those of hmac_item's _MC modes + burst_final_mc_kernel, bit for bit; there
+ * is no rec form.
+ */
+struct BwDgramMc {
+	uint32_t st, seq, fl;
+	bool ok, hashed, alt;
+	bool ciph;		/* RX: the connection has a cipher key */
+	uint64_t off;		/* datagram start */
+	uint32_t mlen;		/* message bytes after header and hash field */
+	const Net2KeyEnt *ent;	/* the connection's entry (entry 0 when the
+				 * index is out of range: never used then) */
+};
+
+template <int MODE, uint32_t DLEN>
+__device__ __forceinline__ BwDgramMc bw_decode_mc(
+    const uint8_t *__restrict__ base, const uint64_t *__restrict__ offsets,
+    const uint32_t *__restrict__ lens, uint64_t i,
+    const uint32_t *__restrict__ seq, const uint32_t *__restrict__ flags,
+    const KeyTabArgs &kt)
+{
+	BwDgramMc g;
+	g.off = offsets[i];
+	const uint32_t len = lens[i];
+	const uint8_t *p = base + g.off;
+	g.st = PKT_OK;
+	g.seq = g.fl = 0;
+	g.alt = g.ciph = false;
+	bool inr;
+	g.ent = keytab_ent(kt, i, &inr);
+	if (MODE == HMAC_BURST_TX_MC) {
+		g.seq = seq[i];
+		g.fl = flags[i];
+		const bool sg = (g.fl & PKT_PH_SIGNED) != 0;
+		const bool cr = (g.fl & PKT_PH_ENCRYPTED) != 0;
+		const uint32_t bits = inr ? g.ent->meta[0] : 0u;
+		if ((bits & NET2_KT_TX) == 0)
+			g.st = PKT_NOCONN;	/* the slot has no tx key */
+		else if (!sg || cr != ((bits & NET2_KT_TX_ENC) != 0))
+			g.st = PKT_UNSAFE;
+		else if (len < 8 + DLEN)
+			g.st = PKT_RESOURCE;	/* no room for header and hash */
+	} else {
+		if (len < 8) {
+			g.st = PKT_BAD;		/* header decode fails */
+		} else {
+			g.seq = load_be32_bytes(p);
+			g.fl = load_be32_bytes(p + 4);
+		}
+		/* the connection's entry, looked at once the header is decoded
+		 * (packet.n2t:210) */
+		const uint4 mt = *reinterpret_cast<const uint4 *>(g.ent->meta);
+		const uint32_t bits = inr ? mt.x : 0u;
+		g.alt = g.st == PKT_OK &&
+		    keytab_rx_alt(bits, mt.y, mt.z, g.seq, g.fl);
+		g.ciph = (bits & NET2_KT_RX_ENC) != 0;
+		if (g.st == PKT_OK && (bits & NET2_KT_RX) == 0)
+			g.st = PKT_NOCONN;	/* no rx key: nothing hashed */
+		if (g.st == PKT_OK && ((g.fl & PKT_PH_SIGNED) == 0 ||
+		    (g.ciph && (g.fl & PKT_PH_ENCRYPTED) == 0)))
+			g.st = PKT_UNSAFE;
+	}
+	g.ok = g.st == PKT_OK;
+	/* after the header: hash field, then message */
+	const uint32_t rlen = g.ok ? len - 8 : 0;
+	g.hashed = g.ok && rlen >= DLEN;
+	g.mlen = g.hashed ? rlen - DLEN : 0;
+	return g;
+}
+
+template <class H, int MODE, bool IS384>
+__global__ __launch_bounds__(128) void burst_wave_mc_kernel(
+    const uint8_t *__restrict__ base, const uint64_t *__restrict__ offsets,
+    const uint32_t *__restrict__ lens, uint64_t n, uint32_t G,
+    const uint32_t *__restrict__ conn, const Net2KeyEnt *__restrict__ tab,
+    uint32_t slots, uint32_t *seq, uint32_t *flags,
+    uint8_t *__restrict__ result, uint8_t *__restrict__ iv, uint32_t ivlen,
+    uint8_t *__restrict__ out)
+{
+	constexpr int NW32 = H::NW32;
+	typedef typename H::word W;
+	constexpr int ROW = sizeof(W) == 4 ? NET2_JOB_ROW256 : NET2_JOB_ROW512;
+	constexpr uint32_t dlen = sizeof(W) == 4 ? 32 : IS384 ? 48 : 64;
+	constexpr bool RX = MODE == HMAC_BURST_RX_MC;
+	__shared__ W rows[BW_ROWS * ROW];
+	__shared__ uint32_t ivw[BW_GMAX][16];
+	__shared__ uint64_t geo_m[BW_GMAX];	/* message start (offset) */
+	__shared__ uint32_t geo_len[BW_GMAX], geo_nb[BW_GMAX];
+	if (sizeof(W) == 8)
+		k512_lds_fill();	/* (synchronises the workgroup) */
+	const uint32_t lane = threadIdx.x & 63;
+	const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+	/* as burst_wave_kernel: slot lane % G, lane d < G owns slot d's stores */
+	const uint32_t dl = lane % G;
+	const uint64_t i = (uint64_t)blockIdx.x * G + dl;
+	const bool live = i < n;
+	const bool mine = lane < G && live;	/* this lane stores datagram i */
+	const KeyTabArgs kt = { conn, tab, slots };
+	BwDgramMc g = {};
+	if (live)
+		g = bw_decode_mc<MODE, dlen>(base, offsets, lens, i, seq, flags, kt);
+
+	if (wv == 1) {
+		/* RX: the IV of an encrypted datagram that may verify, on a
+		 * connection with a cipher key */
+		if (RX && mine && g.ok && g.ciph && ivlen > 0 && iv != nullptr &&
+		    (g.fl & PKT_PH_ENCRYPTED))
+			ph_iv_one(g.seq, g.fl, ivlen,
+			    reinterpret_cast<uint8_t *>(ivw[lane]));
+		__syncthreads();
+		return;
+	}
+
+	/* wave 0: HMAC of every owned message from its connection's ipad
+	 * midstate (a datagram already refused, or without room for its hash
+	 * field, hashes nothing and loads no midstate) */
+	const uint32_t nfull = g.mlen / H::BLOCK;
+	const uint32_t rem = g.mlen % H::BLOCK;
+	const uint32_t nb = !g.hashed ? 0 : nfull + 1 +
+	    (rem >= (uint32_t)(H::BLOCK - H::LENBYTES) ? 1 : 0);
+	if (lane < G) {
+		geo_m[lane] = g.off + 8 + dlen;
+		geo_len[lane] = g.mlen;
+		geo_nb[lane] = live ? nb : 0;
+	}
+	wave_lds_sync();
+	uint32_t nbmax = 0;
+	for (uint32_t d = 0; d < G; d++)
+		nbmax = max(nbmax, geo_nb[d]);
+	nbmax = __builtin_amdgcn_readfirstlane(nbmax);
+	const uint32_t K = BW_ROWS / G;
+	typename H::State s;
+#pragma unroll
+	for (int j = 0; j < 8; j++)
+		s[j] = 0;
+	if (g.hashed)
+		load_mid_tab<H>(RX ? g.ent->rx[g.alt ? 2 : 0] : g.ent->tx[0], s);
+	for (uint32_t c0 = 0; c0 < nbmax; c0 += K) {
+		/* row `lane`: block c0 + lane % K of datagram lane / K */
+		const uint32_t d = lane / K, k = c0 + lane % K;
+		if (d < G && k < geo_nb[d]) {
+			const uint32_t ml = geo_len[d];
+			uint32_t w[NW32];
+			bw_block<H>(base + geo_m[d], k, ml / H::BLOCK, ml % H::BLOCK,
+			    geo_nb[d], ((uint64_t)ml + H::BLOCK) << 3, w);
+			sched_row<H>(w, rows + lane * ROW);
+		}
+		wave_lds_sync();
+		const uint32_t cnt = min(K, nbmax - c0);
+		for (uint32_t b = 0; b < cnt; b++)
+			if (c0 + b < nb)
+				rounds_row<H>(s, rows + (dl * K + b) * ROW);
+		wave_lds_sync();
+	}
+	/* outer: one block = inner digest || 0x80 || 0... || bit count, from the
+	 * opad midstate of the key the inner hash ran under */
+	if (g.hashed) {
+		uint32_t w[NW32];
+#pragma unroll
+		for (int j = 0; j < NW32; j++)
+			w[j] = 0;
+		const int dw = digest_words<H>(s, IS384, w);
+#pragma unroll
+		for (int j = 12; j < 16; j++)		/* SHA-384 keeps 12 words */
+			if (j >= dw)
+				w[j] = 0;
+		w[dw] = 0x80000000u;
+		const uint64_t obits = (uint64_t)(H::BLOCK + 4 * dw) << 3;
+		w[NW32 - 2] = (uint32_t)(obits >> 32);
+		w[NW32 - 1] = (uint32_t)obits;
+		load_mid_tab<H>(RX ? g.ent->rx[g.alt ? 3 : 1] : g.ent->tx[1], s);
+		H::compress(s, w);
+	}
+	materialize<H>(s);
+	uint32_t o[16];
+	H::out_words(s, o, IS384);
+	__syncthreads();		/* wave 1's IVs are in LDS */
+	if (!mine)
+		return;
+	const uint8_t *field = base + g.off + 8;
+	if (RX) {
+		uint32_t code = g.st;
+		if (g.ok) {		/* net2_buffer_cmp, packet.n2t:253-257 */
+			uint32_t diff = 0;
+			if (g.hashed) {
+#pragma unroll
+				for (uint32_t j = 0; j < dlen; j++)
+					diff |= field[j] ^
+					    ((o[j >> 2] >> (8 * (j & 3))) & 0xffu);
+			}
+			code = !g.hashed || diff != 0 ? PKT_BAD : PKT_OK;
+		}
+		if (seq != nullptr) {
+			seq[i] = g.seq;
+			flags[i] = g.fl;
+		}
+		if (code == PKT_OK && g.ciph && ivlen > 0 && iv != nullptr &&
+		    (g.fl & PKT_PH_ENCRYPTED)) {
+			const uint8_t *src = reinterpret_cast<const uint8_t *>(ivw[lane]);
+			uint8_t *dst = iv + i * ivlen;
+			for (uint32_t b = 0; b < ivlen; b++)
+				dst[b] = src[b];
+		}
+		result[i] = (uint8_t)code;
+		return;
+	}
+	/* TX: a slot that is not sealed (NOCONN included) is left untouched */
+	if (g.hashed) {
+		uint8_t *h = out + g.off;
+#pragma unroll
+		for (int b = 0; b < 4; b++) {
+			h[b] = (uint8_t)(g.seq >> (24 - 8 * b));
+			h[4 + b] = (uint8_t)(g.fl >> (24 - 8 * b));
+		}
+		store_digest<dlen>(h + 8, o);
+	}
+	result[i] = (uint8_t)g.st;
+}
+
 /* ---- length binning (counting sort by block count, longest first) ---- */
 
 __device__ __forceinline__ uint32_t bin_of(uint32_t len, int blk_shift,
@@ -3259,6 +3492,16 @@ static uint64_t device_simds()
 	return (uint64_t)c * 4;
 }
 
+/* Datagrams per workgroup of the wave forms (burst_wave_kernel and
+ * burst_wave_mc_kernel) for a burst of n: about one workgroup per SIMD, 1 to
+ * BW_GMAX. */
+static uint32_t burst_wave_group(uint64_t n)
+{
+	const uint64_t simds = std::max<uint64_t>(device_simds(), 1);
+	return (uint32_t)std::min<uint64_t>(BW_GMAX,
+	    std::max<uint64_t>(1, (n + simds - 1) / simds));
+}
+
 /* net2_sha2_burst_limits' setting (-1: none) */
 static std::atomic<int64_t> g_burst_wave_max{-1};
 
@@ -3314,10 +3557,7 @@ hipError_t net2_launch_burst_wave(int alg, const uint8_t *key, size_t keylen,
 				ab[4 * j + b] = (uint8_t)(args->altkey[j] >> (24 - 8 * b));
 		hmac_midstates(halg, ab, &hm, 2);
 	}
-	/* datagrams per workgroup: about one workgroup per SIMD */
-	const uint64_t simds = std::max<uint64_t>(device_simds(), 1);
-	const uint32_t G = (uint32_t)std::min<uint64_t>(BW_GMAX,
-	    std::max<uint64_t>(1, (n + simds - 1) / simds));
+	const uint32_t G = burst_wave_group(n);
 	if (halg == NET2_ALG_SHA256)
 		launch_burst_wave<Sha256H, false>(mode, n, G, s, base, offsets,
 		    lens, hm, *args, result, iv, ivlen, out);
@@ -3327,6 +3567,55 @@ hipError_t net2_launch_burst_wave(int alg, const uint8_t *key, size_t keylen,
 	else
 		launch_burst_wave<Sha512H, false>(mode, n, G, s, base, offsets,
 		    lens, hm, *args, result, iv, ivlen, out);
+	return hipGetLastError();
+}
+
+template <class H, bool IS384>
+static void launch_burst_wave_mc(int mode, uint64_t n, uint32_t G, hipStream_t s,
+    const uint8_t *base, const uint64_t *offsets, const uint32_t *lens,
+    const KeyTabArgs &kt, const BurstArgs &a, uint8_t *result, uint8_t *iv,
+    uint32_t ivlen, uint8_t *out)
+{
+	const unsigned grid = (unsigned)((n + G - 1) / G);
+	if (mode == HMAC_BURST_RX)
+		burst_wave_mc_kernel<H, HMAC_BURST_RX_MC, IS384><<<grid, 128, 0, s>>>(
+		    base, offsets, lens, n, G, kt.conn, kt.tab, kt.slots, a.seq,
+		    a.flags, result, iv, ivlen, out);
+	else
+		burst_wave_mc_kernel<H, HMAC_BURST_TX_MC, IS384><<<grid, 128, 0, s>>>(
+		    base, offsets, lens, n, G, kt.conn, kt.tab, kt.slots, a.seq,
+		    a.flags, result, iv, ivlen, out);
+}
+
+hipError_t net2_launch_burst_wave_mc(int alg, const KeyTabArgs &kt,
+    const uint8_t *base, const uint64_t *offsets, const uint32_t *lens,
+    uint64_t n, const BurstArgs &args, uint8_t *result, uint8_t *iv,
+    uint32_t ivlen, uint8_t *out, int mode, hipStream_t s)
+{
+	const int halg = alg - 3;	/* HMAC row -> SHA row */
+	if ((mode != HMAC_BURST_RX && mode != HMAC_BURST_TX) ||
+	    halg < NET2_ALG_SHA256 || halg > NET2_ALG_SHA512 ||
+	    offsets == nullptr || kt.conn == nullptr || kt.tab == nullptr ||
+	    kt.slots == 0 || args.rec != nullptr || result == nullptr ||
+	    ivlen > 64 || n > 0xffffffffu)
+		return hipErrorInvalidValue;
+	/* RX: the decoded headers to both arrays or to neither; TX: both are
+	 * the inputs, and the sealed datagrams need somewhere to go */
+	if ((args.seq == nullptr) != (args.flags == nullptr) ||
+	    (mode == HMAC_BURST_TX && (args.seq == nullptr || out == nullptr)))
+		return hipErrorInvalidValue;
+	if (n == 0)
+		return hipSuccess;
+	const uint32_t G = burst_wave_group(n);
+	if (halg == NET2_ALG_SHA256)
+		launch_burst_wave_mc<Sha256H, false>(mode, n, G, s, base, offsets,
+		    lens, kt, args, result, iv, ivlen, out);
+	else if (halg == NET2_ALG_SHA384)
+		launch_burst_wave_mc<Sha512H, true>(mode, n, G, s, base, offsets,
+		    lens, kt, args, result, iv, ivlen, out);
+	else
+		launch_burst_wave_mc<Sha512H, false>(mode, n, G, s, base, offsets,
+		    lens, kt, args, result, iv, ivlen, out);
 	return hipGetLastError();
 }
 

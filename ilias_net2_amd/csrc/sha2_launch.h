@@ -182,7 +182,8 @@ hipError_t net2_launch_keytab_set(int alg, Net2KeyEnt *ent, uint32_t side,
  * kt.conn[i] of the table.  mode NET2_HMAC_MODE_BURST_RX / _TX; args: seq,
  * flags, status as for net2_launch_hmac (its key fields and rec are
  * unused); status NET2_PBURST_NOCONN (5) where the slot has no such side.
- * Always the lane form; ws as for net2_launch_var.
+ * The lane form (one datagram per lane; small bursts: net2_launch_burst_wave_mc
+ * below); ws as for net2_launch_var.
  */
 hipError_t net2_launch_hmac_mc(int alg, const KeyTabArgs &kt,
     const uint8_t *base, const uint64_t *offsets, const uint32_t *lens,
@@ -205,7 +206,21 @@ hipError_t net2_launch_burst_wave(int alg, const uint8_t *key, size_t keylen,
     const uint8_t *base, const uint64_t *offsets, const uint32_t *lens,
     uint64_t n, const BurstArgs *args, uint8_t *result, uint8_t *iv,
     uint32_t ivlen, uint8_t *out, int mode, hipStream_t s);
-/* The largest burst net2_launch_burst_wave is for on the current device:
+/*
+ * The same for bursts over many connections
+ * (net2_packet_{decode,encode}_burst_mc, burst_wave_mc_kernel): the keys of
+ * datagram i from entry kt.conn[i] of the table, codes as
+ * net2_launch_hmac_mc + net2_launch_burst_final_mc give them
+ * (NET2_PBURST_NOCONN included), in one launch.  n <= 0xffffffff; of args
+ * only seq / flags are used (RX: the decoded headers, both or neither; TX:
+ * the inputs) and rec must be NULL; iv: RX, written only for an OK
+ * PH_ENCRYPTED datagram whose connection has a cipher key.
+ */
+hipError_t net2_launch_burst_wave_mc(int alg, const KeyTabArgs &kt,
+    const uint8_t *base, const uint64_t *offsets, const uint32_t *lens,
+    uint64_t n, const BurstArgs &args, uint8_t *result, uint8_t *iv,
+    uint32_t ivlen, uint8_t *out, int mode, hipStream_t s);
+/* The largest burst the two wave launchers are for on the current device:
  * 16 datagrams per SIMD, unless net2_sha2_burst_limits set a limit
  * (net2_set_burst_wave_max; < 0 clears it) or NET2_BURST_WAVE_MAX was in
  * the environment at first use (0: never). */

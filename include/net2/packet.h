@@ -76,9 +76,23 @@ size_t net2_packet_burst_workspace(uint64_t n);
  * are length-binned first.  A value < 0 restores that threshold's default
  * (16 datagrams per SIMD / 65,536, or NET2_BURST_WAVE_MAX /
  * NET2_BURST_BIN_MIN when set in the environment at first use).  Results do
- * not depend on either; only the time does.  Always 0.
+ * not depend on either; only the time does.  Both apply to the
+ * single-connection calls, their _host pipelines and the _mc calls below
+ * alike.  Always 0.
  */
 int net2_sha2_burst_limits(int64_t wave_max, int64_t bin_min);
+
+/*
+ * Keyed hash-burst launches of this process so far, by form (either pointer
+ * may be NULL): lane_launches counts the one-datagram-per-lane kernel,
+ * wave_launches the one-launch small-burst form -- one per keyed pass through
+ * net2_packet_{decode,encode}_burst[_ck], per chunk of their _host pipelines,
+ * and per net2_packet_{decode,encode}_burst_mc call.  Bursts without a hash
+ * key, calls with n == 0 and calls refused by their argument checks count
+ * nothing.  The only way to tell which form a call took.  Host state: needs
+ * no device.  Always 0.
+ */
+int net2_sha2_burst_stats(uint64_t *lane_launches, uint64_t *wave_launches);
 
 /*
  * RX: the hash steps of net2_packet_decode for a burst of n received
@@ -328,9 +342,14 @@ int net2_burst_keytab_clear(struct net2_burst_keytab *tab, uint32_t slot,
  *   otherwise its header is decoded (d_seq / d_flags), and without a
  *   connection it is NET2_PBURST_NOCONN: nothing hashed, no IV written.
  *   TX: a slot without a connection is NET2_PBURST_NOCONN and left untouched.
- * These calls always hash one datagram per lane: net2_sha2_burst_limits'
- * bin_min applies, wave_max does not (the one-launch small-burst form and
- * the _host pipelines remain single-connection).
+ * Both forms of the single-connection calls exist here: a burst of at most
+ * net2_sha2_burst_limits' wave_max datagrams (default: 16 per SIMD of the
+ * device) is hashed 1 to 16 datagrams per workgroup in one launch, the keys
+ * read from the table by every workgroup, and does not touch the workspace
+ * (which is required and checked all the same); a larger one is hashed one
+ * datagram per lane, and bin_min applies.  Results do not depend on the
+ * form; net2_sha2_burst_stats tells which one a call took.  Only the _host
+ * pipelines remain single-connection.
  * EINVAL also when the calling thread's device is not the table's.
  */
 int net2_packet_decode_burst_mc(const struct net2_burst_keytab *tab,
