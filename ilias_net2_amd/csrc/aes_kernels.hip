@@ -39,6 +39,7 @@
 #include "aes_sched.h"
 #include "aes_tab.h"
 #include "aes_wave.h"
+#include "key_wipe.h"
 
 #include <stddef.h>
 #include <string.h>
@@ -860,23 +861,16 @@ __global__ __launch_bounds__(64) void aes_tab_set_kernel(Net2CipherEnt *ent,
 	}
 }
 
-void wipe(void *p, size_t n)
-{
-	volatile uint8_t *z = (volatile uint8_t *)p;
-	while (n-- > 0)
-		*z++ = 0;
-}
+/* ---- what the launchers share -------------------------------------------- */
 
-}	/* namespace */
-
-hipError_t net2_launch_aes_decrypt(const uint8_t *key, const AesRxAlt &alt,
-    uint32_t hashlen, const uint8_t *base, const uint64_t *offsets,
-    const uint32_t *lens, uint64_t n, const uint32_t *seq,
-    const uint32_t *flags, const uint8_t *iv, uint8_t *result, uint8_t *out,
-    uint32_t *plen, hipStream_t s)
+/* A decrypt burst's arguments; alt: the alternate key's cutoff (the launches
+ * under one connection's keys; NULL: the _mc launches, which take it from
+ * the table). */
+AesBurstArgs decrypt_args(const AesRxAlt *alt, uint32_t hashlen,
+    const uint8_t *base, const uint64_t *offsets, const uint32_t *lens,
+    uint64_t n, const uint32_t *seq, const uint32_t *flags, const uint8_t *iv,
+    uint8_t *result, uint8_t *out, uint32_t *plen)
 {
-	if (n == 0)
-		return hipSuccess;
 	AesBurstArgs a = {};
 	a.in = base;
 	a.out = out;
@@ -889,34 +883,19 @@ hipError_t net2_launch_aes_decrypt(const uint8_t *key, const AesRxAlt &alt,
 	a.plen = plen;
 	a.n = n;
 	a.hashlen = hashlen;
-	a.no_cutoff = alt.no_cutoff != 0;
-	a.cutoff = alt.cutoff;
-	a.rx_start = alt.rx_start;
-	const dim3 grid((unsigned)((n + AES_WG - 1) / AES_WG));
-	if (alt.alt_key != nullptr) {
-		AesKeys<2> k;
-		aes256_dec_schedule(key, &k.k[0]);
-		aes256_dec_schedule(alt.alt_key, &k.k[1]);
-		hipLaunchKernelGGL(aes_cbc_decrypt_kernel<true>, grid, dim3(AES_WG),
-		    0, s, a, k);
-		wipe(&k, sizeof(k));
-	} else {
-		AesKeys<1> k;
-		aes256_dec_schedule(key, &k.k[0]);
-		hipLaunchKernelGGL(aes_cbc_decrypt_kernel<false>, grid, dim3(AES_WG),
-		    0, s, a, k);
-		wipe(&k, sizeof(k));
+	if (alt != nullptr) {
+		a.no_cutoff = alt->no_cutoff != 0;
+		a.cutoff = alt->cutoff;
+		a.rx_start = alt->rx_start;
 	}
-	return hipGetLastError();
+	return a;
 }
 
-hipError_t net2_launch_aes_encrypt(const uint8_t *key, uint32_t hashlen,
-    const uint32_t *flags, const uint8_t *iv, uint8_t *base,
-    const uint64_t *offsets, const uint32_t *lens, const uint32_t *plen,
-    uint64_t n, uint8_t *result, uint32_t *wire_len, hipStream_t s)
+AesBurstArgs encrypt_args(uint32_t hashlen, const uint32_t *flags,
+    const uint8_t *iv, uint8_t *base, const uint64_t *offsets,
+    const uint32_t *lens, const uint32_t *plen, uint64_t n, uint8_t *result,
+    uint32_t *wire_len)
 {
-	if (n == 0)
-		return hipSuccess;
 	AesBurstArgs a = {};
 	a.out = base;
 	a.offsets = offsets;
@@ -928,67 +907,30 @@ hipError_t net2_launch_aes_encrypt(const uint8_t *key, uint32_t hashlen,
 	a.wire_len = wire_len;
 	a.n = n;
 	a.hashlen = hashlen;
-	AesKeys<1> k;
-	aes256_enc_schedule(key, &k.k[0]);
-	hipLaunchKernelGGL(aes_cbc_encrypt_kernel,
-	    dim3((unsigned)((n + AES_WG - 1) / AES_WG)), dim3(AES_WG), 0, s, a, k);
-	wipe(&k, sizeof(k));
-	return hipGetLastError();
+	return a;
 }
 
-hipError_t net2_launch_aes_tab_set(Net2CipherEnt *ents, uint32_t slot,
-    uint32_t side, const uint8_t *key, const uint8_t *alt_key, int no_cutoff,
-    uint32_t cutoff, uint32_t rx_start, hipStream_t s)
+AesMcArgs mc_args(const AesBurstArgs &b, const AesTabArgs &kt)
 {
-	if (ents == nullptr || (side != 0 && key == nullptr))
-		return hipErrorInvalidValue;
-	Net2CipherEnt nw = {};
-	if (side == NET2_AES_TAB_RX)
-		aes_tab_fill_rx(&nw, key, alt_key, no_cutoff != 0, cutoff, rx_start);
-	else if (side == NET2_AES_TAB_TX)
-		aes_tab_fill_tx(&nw, key);
-	hipLaunchKernelGGL(aes_tab_set_kernel, dim3(1), dim3(64), 0, s, ents + slot,
-	    side, nw);
-	wipe(&nw, sizeof(nw));
-	return hipGetLastError();
-}
-
-hipError_t net2_launch_aes_decrypt_mc(const AesTabArgs &kt, uint32_t hashlen,
-    const uint8_t *base, const uint64_t *offsets, const uint32_t *lens,
-    uint64_t n, const uint32_t *seq, const uint32_t *flags, const uint8_t *iv,
-    uint8_t *result, uint8_t *out, uint32_t *plen, hipStream_t s)
-{
-	if (n == 0)
-		return hipSuccess;
 	AesMcArgs m = {};
-	m.b.in = base;
-	m.b.out = out;
-	m.b.offsets = offsets;
-	m.b.lens = lens;
-	m.b.seq = seq;
-	m.b.flags = flags;
-	m.b.iv = iv;
-	m.b.result = result;
-	m.b.plen = plen;
-	m.b.n = n;
-	m.b.hashlen = hashlen;
+	m.b = b;
 	m.conn = kt.conn;
 	m.tab = kt.tab;
 	m.slots = kt.slots;
-	hipLaunchKernelGGL(aes_cbc_decrypt_mc_kernel,
-	    dim3((unsigned)((n + AES_WG - 1) / AES_WG)), dim3(AES_WG), 0, s, m);
-	return hipGetLastError();
+	return m;
 }
 
-/* ---- the wave form of the decrypt launches ---------------------------------- */
-
-namespace {
+/* The lane forms' grid: one lane per datagram. */
+dim3 lane_grid(uint64_t n)
+{
+	return dim3((unsigned)((n + AES_WG - 1) / AES_WG));
+}
 
 /*
- * Datagrams per wave (the kernel's per_wave) and the grid for a burst of n:
- * one datagram per wave until the grid would pass AES_WAVE_GRID workgroups
- * (five of them, 32 KiB of table each, are resident per CU of an MI355X's
- * 256), then as many as keep it there, 16 at the most.
+ * The wave form's datagrams per wave (the kernel's per_wave) and grid for a
+ * burst of n: one datagram per wave until the grid would pass AES_WAVE_GRID
+ * workgroups (five of them, 32 KiB of table each, are resident per CU of an
+ * MI355X's 256), then as many as keep it there, 16 at the most.
  */
 constexpr uint64_t AES_WAVE_GRID = 1280;
 constexpr uint64_t AES_WAVE_PER_MAX = 16;
@@ -1006,7 +948,100 @@ dim3 wave_grid(uint64_t n, uint32_t per)
 	return dim3((unsigned)((n + step - 1) / step));
 }
 
+/*
+ * The decrypt launches under one connection's keys, either form: the rx
+ * schedules (key, and alt_key when there is one: NK = 2) expanded into k,
+ * which is or lies in the launch's arguments; launch(); the schedules wiped,
+ * the launch having copied its arguments.
+ */
+template <int NK, class L>
+void launch_rx_keyed(const uint8_t *key, const uint8_t *alt_key, AesKeys<NK> &k,
+    L &&launch)
+{
+	aes256_dec_schedule(key, &k.k[0]);
+	if constexpr (NK == 2)
+		aes256_dec_schedule(alt_key, &k.k[1]);
+	launch();
+	key_wipe(&k, sizeof(k));
+}
+
 }	/* namespace */
+
+hipError_t net2_launch_aes_decrypt(const uint8_t *key, const AesRxAlt &alt,
+    uint32_t hashlen, const uint8_t *base, const uint64_t *offsets,
+    const uint32_t *lens, uint64_t n, const uint32_t *seq,
+    const uint32_t *flags, const uint8_t *iv, uint8_t *result, uint8_t *out,
+    uint32_t *plen, hipStream_t s)
+{
+	if (n == 0)
+		return hipSuccess;
+	const AesBurstArgs a = decrypt_args(&alt, hashlen, base, offsets, lens, n,
+	    seq, flags, iv, result, out, plen);
+	if (alt.alt_key != nullptr) {
+		AesKeys<2> k;
+		launch_rx_keyed(key, alt.alt_key, k, [&] {
+			hipLaunchKernelGGL(aes_cbc_decrypt_kernel<true>, lane_grid(n),
+			    dim3(AES_WG), 0, s, a, k);
+		});
+	} else {
+		AesKeys<1> k;
+		launch_rx_keyed(key, nullptr, k, [&] {
+			hipLaunchKernelGGL(aes_cbc_decrypt_kernel<false>, lane_grid(n),
+			    dim3(AES_WG), 0, s, a, k);
+		});
+	}
+	return hipGetLastError();
+}
+
+hipError_t net2_launch_aes_encrypt(const uint8_t *key, uint32_t hashlen,
+    const uint32_t *flags, const uint8_t *iv, uint8_t *base,
+    const uint64_t *offsets, const uint32_t *lens, const uint32_t *plen,
+    uint64_t n, uint8_t *result, uint32_t *wire_len, hipStream_t s)
+{
+	if (n == 0)
+		return hipSuccess;
+	const AesBurstArgs a = encrypt_args(hashlen, flags, iv, base, offsets,
+	    lens, plen, n, result, wire_len);
+	AesKeys<1> k;
+	aes256_enc_schedule(key, &k.k[0]);
+	hipLaunchKernelGGL(aes_cbc_encrypt_kernel, lane_grid(n), dim3(AES_WG), 0, s,
+	    a, k);
+	key_wipe(&k, sizeof(k));
+	return hipGetLastError();
+}
+
+hipError_t net2_launch_aes_tab_set(Net2CipherEnt *ents, uint32_t slot,
+    uint32_t side, const uint8_t *key, const uint8_t *alt_key, int no_cutoff,
+    uint32_t cutoff, uint32_t rx_start, hipStream_t s)
+{
+	if (ents == nullptr || (side != 0 && key == nullptr))
+		return hipErrorInvalidValue;
+	Net2CipherEnt nw = {};
+	if (side == NET2_AES_TAB_RX)
+		aes_tab_fill_rx(&nw, key, alt_key, no_cutoff != 0, cutoff, rx_start);
+	else if (side == NET2_AES_TAB_TX)
+		aes_tab_fill_tx(&nw, key);
+	hipLaunchKernelGGL(aes_tab_set_kernel, dim3(1), dim3(64), 0, s, ents + slot,
+	    side, nw);
+	key_wipe(&nw, sizeof(nw));
+	return hipGetLastError();
+}
+
+hipError_t net2_launch_aes_decrypt_mc(const AesTabArgs &kt, uint32_t hashlen,
+    const uint8_t *base, const uint64_t *offsets, const uint32_t *lens,
+    uint64_t n, const uint32_t *seq, const uint32_t *flags, const uint8_t *iv,
+    uint8_t *result, uint8_t *out, uint32_t *plen, hipStream_t s)
+{
+	if (n == 0)
+		return hipSuccess;
+	const AesMcArgs m = mc_args(decrypt_args(nullptr, hashlen, base, offsets,
+	    lens, n, seq, flags, iv, result, out, plen), kt);
+	hipLaunchKernelGGL(aes_cbc_decrypt_mc_kernel, lane_grid(n), dim3(AES_WG), 0,
+	    s, m);
+	return hipGetLastError();
+}
+
+/* ---- the wave form of the decrypt launches ---------------------------------- */
 
 hipError_t net2_launch_aes_decrypt_wave(const uint8_t *key, const AesRxAlt &alt,
     uint32_t hashlen, const uint8_t *base, const uint64_t *offsets,
@@ -1016,37 +1051,23 @@ hipError_t net2_launch_aes_decrypt_wave(const uint8_t *key, const AesRxAlt &alt,
 {
 	if (n == 0)
 		return hipSuccess;
-	AesBurstArgs a = {};
-	a.in = base;
-	a.out = out;
-	a.offsets = offsets;
-	a.lens = lens;
-	a.seq = seq;
-	a.flags = flags;
-	a.iv = iv;
-	a.result = result;
-	a.plen = plen;
-	a.n = n;
-	a.hashlen = hashlen;
-	a.no_cutoff = alt.no_cutoff != 0;
-	a.cutoff = alt.cutoff;
-	a.rx_start = alt.rx_start;
+	const AesBurstArgs a = decrypt_args(&alt, hashlen, base, offsets, lens, n,
+	    seq, flags, iv, result, out, plen);
 	const uint32_t per = wave_per(n);
 	if (alt.alt_key != nullptr) {
 		AesWaveArgs<KS_ALT> w;
 		w.b = a;
-		aes256_dec_schedule(key, &w.keys.k[0]);
-		aes256_dec_schedule(alt.alt_key, &w.keys.k[1]);
-		hipLaunchKernelGGL(aes_cbc_decrypt_wave_kernel<KS_ALT>, wave_grid(n, per),
-		    dim3(AES_WG), 0, s, w, per);
-		wipe(&w.keys, sizeof(w.keys));
+		launch_rx_keyed(key, alt.alt_key, w.keys, [&] {
+			hipLaunchKernelGGL(aes_cbc_decrypt_wave_kernel<KS_ALT>,
+			    wave_grid(n, per), dim3(AES_WG), 0, s, w, per);
+		});
 	} else {
 		AesWaveArgs<KS_ONE> w;
 		w.b = a;
-		aes256_dec_schedule(key, &w.keys.k[0]);
-		hipLaunchKernelGGL(aes_cbc_decrypt_wave_kernel<KS_ONE>, wave_grid(n, per),
-		    dim3(AES_WG), 0, s, w, per);
-		wipe(&w.keys, sizeof(w.keys));
+		launch_rx_keyed(key, nullptr, w.keys, [&] {
+			hipLaunchKernelGGL(aes_cbc_decrypt_wave_kernel<KS_ONE>,
+			    wave_grid(n, per), dim3(AES_WG), 0, s, w, per);
+		});
 	}
 	return hipGetLastError();
 }
@@ -1060,20 +1081,8 @@ hipError_t net2_launch_aes_decrypt_mc_wave(const AesTabArgs &kt,
 	if (n == 0)
 		return hipSuccess;
 	AesWaveArgs<KS_TAB> w = {};
-	w.m.b.in = base;
-	w.m.b.out = out;
-	w.m.b.offsets = offsets;
-	w.m.b.lens = lens;
-	w.m.b.seq = seq;
-	w.m.b.flags = flags;
-	w.m.b.iv = iv;
-	w.m.b.result = result;
-	w.m.b.plen = plen;
-	w.m.b.n = n;
-	w.m.b.hashlen = hashlen;
-	w.m.conn = kt.conn;
-	w.m.tab = kt.tab;
-	w.m.slots = kt.slots;
+	w.m = mc_args(decrypt_args(nullptr, hashlen, base, offsets, lens, n, seq,
+	    flags, iv, result, out, plen), kt);
 	const uint32_t per = wave_per(n);
 	hipLaunchKernelGGL(aes_cbc_decrypt_wave_kernel<KS_TAB>, wave_grid(n, per),
 	    dim3(AES_WG), 0, s, w, per);
@@ -1087,21 +1096,9 @@ hipError_t net2_launch_aes_encrypt_mc(const AesTabArgs &kt, uint32_t hashlen,
 {
 	if (n == 0)
 		return hipSuccess;
-	AesMcArgs m = {};
-	m.b.out = base;
-	m.b.offsets = offsets;
-	m.b.lens = lens;
-	m.b.flags = flags;
-	m.b.iv = iv;
-	m.b.result = result;
-	m.b.plen = const_cast<uint32_t *>(plen);
-	m.b.wire_len = wire_len;
-	m.b.n = n;
-	m.b.hashlen = hashlen;
-	m.conn = kt.conn;
-	m.tab = kt.tab;
-	m.slots = kt.slots;
-	hipLaunchKernelGGL(aes_cbc_encrypt_mc_kernel,
-	    dim3((unsigned)((n + AES_WG - 1) / AES_WG)), dim3(AES_WG), 0, s, m);
+	const AesMcArgs m = mc_args(encrypt_args(hashlen, flags, iv, base, offsets,
+	    lens, plen, n, result, wire_len), kt);
+	hipLaunchKernelGGL(aes_cbc_encrypt_mc_kernel, lane_grid(n), dim3(AES_WG), 0,
+	    s, m);
 	return hipGetLastError();
 }

@@ -34,7 +34,7 @@ NET2_EXPORT int net2_hmac_sign_dev(int alg, const void *key, size_t keylen,
 	    n, d_ws, ws_bytes);
 	if (rc != 0 || n == 0)
 		return rc;
-	HIP_TRY(net2_launch_hmac(alg, (const uint8_t *)key, keylen,
+	HIP_TRY(net2_launch_hmac(alg, (const uint8_t *)key, nullptr, keylen,
 	    (const uint8_t *)d_base, d_offsets, d_lens, 0, 0, n,
 	    (uint8_t *)d_base, (uint32_t *)d_ws, (hipStream_t)stream,
 	    NET2_HMAC_MODE_SIGN));
@@ -52,7 +52,7 @@ NET2_EXPORT int net2_hmac_verify_dev(int alg, const void *key,
 		return rc;
 	if (d_result == nullptr)
 		return EINVAL;
-	HIP_TRY(net2_launch_hmac(alg, (const uint8_t *)key, keylen,
+	HIP_TRY(net2_launch_hmac(alg, (const uint8_t *)key, nullptr, keylen,
 	    (const uint8_t *)d_base, d_offsets, d_lens, 0, 0, n, d_result,
 	    (uint32_t *)d_ws, (hipStream_t)stream, NET2_HMAC_MODE_VERIFY));
 	return 0;
@@ -80,7 +80,7 @@ NET2_EXPORT int net2_hmac_dev(int alg, const void *key, size_t keylen,
 	}
 	if (int rc = check_current_device())
 		return rc;
-	HIP_TRY(net2_launch_hmac(alg, (const uint8_t *)key, keylen,
+	HIP_TRY(net2_launch_hmac(alg, (const uint8_t *)key, nullptr, keylen,
 	    (const uint8_t *)d_base, d_offsets, d_lens, stride, fixed_len, n,
 	    (uint8_t *)d_digests, d_offsets ? (uint32_t *)d_ws : nullptr,
 	    (hipStream_t)stream));
@@ -175,43 +175,43 @@ int check_cipher_keys(const struct net2_burst_cipher_keys *ck)
 	return 0;
 }
 
-/* net2_sha2_burst_limits' binning threshold (-1: none) */
-std::atomic<int64_t> g_burst_bin_min{-1};
+/* net2_sha2_burst_limits' two thresholds, net2_aes_burst_limits' one */
+FormKnob g_burst_wave_max{"NET2_BURST_WAVE_MAX"};
+FormKnob g_burst_bin_min{"NET2_BURST_BIN_MIN"};
+FormKnob g_aes_wave_max{"NET2_AES_WAVE_MAX"};
+
+/* net2_sha2_burst_stats' counts (keyed hash-burst launches) and
+ * net2_aes_burst_stats' (decrypt launches) */
+FormCounts g_burst_launches, g_aes_launches;
 
 /*
  * The binning workspace a burst's HMAC kernel is given: below the binning
  * threshold (default 65,536 datagrams: one lane per datagram, one wave per
  * SIMD) none -- every wave then has a SIMD of its own, the burst takes its
  * longest wave's time whatever the order, and the binning launch is pure
- * fixed cost (tools/burst_sizes.py).  The threshold is
- * net2_sha2_burst_limits' setting, else NET2_BURST_BIN_MIN from the
- * environment at first use (A/B runs), else the default.
+ * fixed cost (tools/burst_sizes.py).
  */
 uint32_t *burst_bins(uint64_t n, uint32_t *bin)
 {
-	int64_t min_n = g_burst_bin_min.load(std::memory_order_relaxed);
-	if (min_n < 0) {
-		static const int64_t env = [] {
-			const char *e = getenv("NET2_BURST_BIN_MIN");
-			return e != nullptr && *e != '\0' ?
-			    (int64_t)(strtoull(e, nullptr, 10) & INT64_MAX) :
-			    (int64_t)65536;
-		}();
-		min_n = env;
-	}
-	return n >= (uint64_t)min_n ? bin : nullptr;
+	return n >= g_burst_bin_min.get(65536) ? bin : nullptr;
 }
 
-/* net2_sha2_burst_stats' counts: keyed hash-burst launches by form */
-std::atomic<uint64_t> g_burst_lane_launches{0}, g_burst_wave_launches{0};
-
-void burst_count_launch(bool wave)
+/* After a keyed hash-burst launch: its form counted, then the fault
+ * injection point of a chunk's first kernel. */
+int burst_launched(bool wave)
 {
-	(wave ? g_burst_wave_launches : g_burst_lane_launches)
-	    .fetch_add(1, std::memory_order_relaxed);
+	g_burst_launches.count(wave);
+	FI_POINT(FI_KERNEL);
+	return 0;
 }
 
 }	/* namespace */
+
+uint64_t net2_burst_wave_max(void)
+{
+	uint64_t v;
+	return g_burst_wave_max.get(&v) ? v : net2_burst_wave_default();
+}
 
 /*
  * The hash steps of net2_packet_decode for a device-resident burst.
@@ -235,48 +235,46 @@ int decode_burst(const struct net2_burst_rx_keys *k, uint32_t ivlen,
 	if (hash_set) {
 		/* header decode, key choice, flag checks and HMAC verify in one
 		 * kernel over the wire datagrams (binned by datagram length) */
+		const uint8_t *const key = (const uint8_t *)k->hash_key;
+		const uint8_t *const altkey =
+		    alt ? (const uint8_t *)k->alt_hash_key : nullptr;
+		/* the kernel's inputs from the connection's keys: no key bytes
+		 * (the launcher turns those into midstates) */
 		BurstArgs rx = {};
-		rx.seq = seq;
-		rx.flags = flags;
-		rx.status = w.status;
 		rx.enc_set = enc_set;
 		if (alt) {
-			const uint8_t *ak = (const uint8_t *)k->alt_hash_key;
 			rx.alt = 1;
 			rx.alt_enc_set = enc_set;
 			rx.no_cutoff = k->alt_no_cutoff != 0;
 			rx.cutoff = k->alt_cutoff;
 			rx.rx_start = k->rx_start;
-			for (size_t i = 0; i < k->alt_hash_keylen; i++)
-				rx.altkey[i / 4] |= (uint32_t)ak[i] << (24 - 8 * (i % 4));
 		}
 		if (wave) {
 			/* a small burst: 1 to 16 datagrams per workgroup,
 			 * codes, headers and IVs stored by that one launch */
 			rx.seq = d_seq;
 			rx.flags = d_flags;
-			rx.status = nullptr;
-			HIP_TRY(net2_launch_burst_wave(hash_alg,
-			    (const uint8_t *)k->hash_key, k->hash_keylen,
-			    (const uint8_t *)d_base, d_offsets, d_lens, n, &rx,
-			    d_result, enc_set ? (uint8_t *)d_iv : nullptr,
-			    enc_set ? ivlen : 0, nullptr, NET2_HMAC_MODE_BURST_RX,
-			    s));
-			burst_count_launch(true);
-			FI_POINT(FI_KERNEL);
-			return 0;
+			HIP_TRY(net2_launch_burst_wave(hash_alg, key, altkey,
+			    k->hash_keylen, (const uint8_t *)d_base, d_offsets,
+			    d_lens, n, &rx, d_result,
+			    enc_set ? (uint8_t *)d_iv : nullptr, enc_set ? ivlen : 0,
+			    nullptr, NET2_HMAC_MODE_BURST_RX, s));
+			return burst_launched(true);
 		}
-		HIP_TRY(net2_launch_hmac(hash_alg, (const uint8_t *)k->hash_key,
-		    k->hash_keylen, (const uint8_t *)d_base, d_offsets, d_lens, 0,
-		    0, n, w.verdict, burst_bins(n, w.bin), s,
-		    NET2_HMAC_MODE_BURST_RX, &rx));
-		burst_count_launch(false);
+		rx.seq = seq;
+		rx.flags = flags;
+		rx.status = w.status;
+		HIP_TRY(net2_launch_hmac(hash_alg, key, altkey, k->hash_keylen,
+		    (const uint8_t *)d_base, d_offsets, d_lens, 0, 0, n, w.verdict,
+		    burst_bins(n, w.bin), s, NET2_HMAC_MODE_BURST_RX, &rx));
+		if (int rc = burst_launched(false))
+			return rc;
 	} else {
 		HIP_TRY(net2_launch_burst_prep((uint8_t *)d_base, d_offsets,
 		    d_lens, n, 0, 0, enc_set, 0, nullptr, nullptr, seq,
 		    flags, w.sub_off, w.sub_len, w.status, s));
+		FI_POINT(FI_KERNEL);
 	}
-	FI_POINT(FI_KERNEL);
 	HIP_TRY(net2_launch_burst_final(n, w.status, w.verdict, seq, flags,
 	    enc_set ? ivlen : 0, (uint8_t *)d_iv, d_result, s,
 	    hdr_out ? d_seq : nullptr, hdr_out ? d_flags : nullptr));
@@ -315,20 +313,16 @@ int encode_burst(int hash_alg, const void *hash_key, size_t hash_keylen,
 		if (wave) {
 			/* a small burst: 1 to 16 datagrams per workgroup */
 			HIP_TRY(net2_launch_burst_wave(hash_alg,
-			    (const uint8_t *)hash_key, hash_keylen,
+			    (const uint8_t *)hash_key, nullptr, hash_keylen,
 			    (const uint8_t *)d_base, d_offsets, d_lens, n, &tx,
 			    d_result, nullptr, 0, out, NET2_HMAC_MODE_BURST_TX, s));
-			burst_count_launch(true);
-			FI_POINT(FI_KERNEL);
-			return 0;
+			return burst_launched(true);
 		}
 		HIP_TRY(net2_launch_hmac(hash_alg, (const uint8_t *)hash_key,
-		    hash_keylen, (const uint8_t *)d_base, d_offsets, d_lens, 0,
-		    0, n, out, bin ? burst_bins(n, w.bin) : nullptr, s,
+		    nullptr, hash_keylen, (const uint8_t *)d_base, d_offsets,
+		    d_lens, 0, 0, n, out, bin ? burst_bins(n, w.bin) : nullptr, s,
 		    NET2_HMAC_MODE_BURST_TX, &tx));
-		burst_count_launch(false);
-		FI_POINT(FI_KERNEL);
-		return 0;
+		return burst_launched(false);
 	}
 	HIP_TRY(net2_launch_burst_prep((uint8_t *)d_base, d_offsets,
 	    d_lens, n, 1, 0, enc_alg != 0, 0, d_seq, d_flags, nullptr,
@@ -346,18 +340,15 @@ NET2_EXPORT size_t net2_packet_burst_workspace(uint64_t n)
 
 NET2_EXPORT int net2_sha2_burst_limits(int64_t wave_max, int64_t bin_min)
 {
-	net2_set_burst_wave_max(wave_max);
-	g_burst_bin_min.store(bin_min < 0 ? -1 : bin_min, std::memory_order_relaxed);
+	g_burst_wave_max.set(wave_max);
+	g_burst_bin_min.set(bin_min);
 	return 0;
 }
 
 NET2_EXPORT int net2_sha2_burst_stats(uint64_t *lane_launches,
     uint64_t *wave_launches)
 {
-	if (lane_launches != nullptr)
-		*lane_launches = g_burst_lane_launches.load(std::memory_order_relaxed);
-	if (wave_launches != nullptr)
-		*wave_launches = g_burst_wave_launches.load(std::memory_order_relaxed);
+	g_burst_launches.read(lane_launches, wave_launches);
 	return 0;
 }
 
@@ -431,50 +422,26 @@ namespace {
  * lane form's own spread (209 against 283 us there; at 262,144 datagrams one
  * lane per datagram fills the device and wins, 493 against 683 us).
  */
-constexpr int64_t AES_WAVE_MAX_DEFAULT = 65536;
+constexpr uint64_t AES_WAVE_MAX_DEFAULT = 65536;
 
-/* net2_aes_burst_limits' setting (-1: none) and net2_aes_burst_stats' counts */
-std::atomic<int64_t> g_aes_wave_max{-1};
-std::atomic<uint64_t> g_aes_lane_launches{0}, g_aes_wave_launches{0};
-
-/* Whether a decrypt burst of n takes the wave form: the setting, else
- * NET2_AES_WAVE_MAX from the environment at first use, else the default. */
+/* Whether a decrypt burst of n takes the wave form. */
 bool aes_wave_form(uint64_t n)
 {
-	int64_t max_n = g_aes_wave_max.load(std::memory_order_relaxed);
-	if (max_n < 0) {
-		static const int64_t env = [] {
-			const char *e = getenv("NET2_AES_WAVE_MAX");
-			return e != nullptr && *e != '\0' ?
-			    (int64_t)(strtoull(e, nullptr, 10) & INT64_MAX) :
-			    AES_WAVE_MAX_DEFAULT;
-		}();
-		max_n = env;
-	}
-	return n <= (uint64_t)max_n;
-}
-
-void aes_count_launch(bool wave)
-{
-	(wave ? g_aes_wave_launches : g_aes_lane_launches)
-	    .fetch_add(1, std::memory_order_relaxed);
+	return n <= g_aes_wave_max.get(AES_WAVE_MAX_DEFAULT);
 }
 
 }	/* namespace */
 
 NET2_EXPORT int net2_aes_burst_limits(int64_t wave_max)
 {
-	g_aes_wave_max.store(wave_max < 0 ? -1 : wave_max, std::memory_order_relaxed);
+	g_aes_wave_max.set(wave_max);
 	return 0;
 }
 
 NET2_EXPORT int net2_aes_burst_stats(uint64_t *lane_launches,
     uint64_t *wave_launches)
 {
-	if (lane_launches != nullptr)
-		*lane_launches = g_aes_lane_launches.load(std::memory_order_relaxed);
-	if (wave_launches != nullptr)
-		*wave_launches = g_aes_wave_launches.load(std::memory_order_relaxed);
+	g_aes_launches.read(lane_launches, wave_launches);
 	return 0;
 }
 
@@ -511,7 +478,7 @@ NET2_EXPORT int net2_packet_decrypt_burst(const struct net2_burst_rx_keys *k,
 	    (const uint8_t *)d_base, d_offsets, d_lens, n, d_seq, d_flags,
 	    (const uint8_t *)d_iv, d_result, (uint8_t *)d_out, d_plen,
 	    (hipStream_t)stream));
-	aes_count_launch(wave);
+	g_aes_launches.count(wave);
 	return 0;
 }
 
@@ -705,9 +672,7 @@ NET2_EXPORT int net2_packet_decode_burst_mc(const struct net2_burst_keytab *tab,
 		HIP_TRY(net2_launch_burst_wave_mc(tab->hash_alg, kt,
 		    (const uint8_t *)d_base, d_offsets, d_lens, n, rx, d_result,
 		    (uint8_t *)d_iv, ivlen, nullptr, NET2_HMAC_MODE_BURST_RX, s));
-		burst_count_launch(true);
-		FI_POINT(FI_KERNEL);
-		return 0;
+		return burst_launched(true);
 	}
 	BurstWs w;
 	burst_layout(n, (uint8_t *)d_ws, &w);
@@ -720,8 +685,8 @@ NET2_EXPORT int net2_packet_decode_burst_mc(const struct net2_burst_keytab *tab,
 	HIP_TRY(net2_launch_hmac_mc(tab->hash_alg, kt, (const uint8_t *)d_base,
 	    d_offsets, d_lens, n, w.verdict, burst_bins(n, w.bin), s,
 	    NET2_HMAC_MODE_BURST_RX, rx));
-	burst_count_launch(false);
-	FI_POINT(FI_KERNEL);
+	if (int rc = burst_launched(false))
+		return rc;
 	/* ... and the final kernel folds the verdicts in and derives the IV
 	 * of every OK PH_ENCRYPTED datagram whose connection has a cipher key
 	 * (one cipher, so one ivlen) */
@@ -750,18 +715,14 @@ NET2_EXPORT int net2_packet_encode_burst_mc(const struct net2_burst_keytab *tab,
 		    (const uint8_t *)d_base, d_offsets, d_lens, n, tx, d_result,
 		    nullptr, 0, (uint8_t *)d_base, NET2_HMAC_MODE_BURST_TX,
 		    (hipStream_t)stream));
-		burst_count_launch(true);
-		FI_POINT(FI_KERNEL);
-		return 0;
+		return burst_launched(true);
 	}
 	BurstWs w;
 	burst_layout(n, (uint8_t *)d_ws, &w);
 	HIP_TRY(net2_launch_hmac_mc(tab->hash_alg, kt, (const uint8_t *)d_base,
 	    d_offsets, d_lens, n, (uint8_t *)d_base, burst_bins(n, w.bin),
 	    (hipStream_t)stream, NET2_HMAC_MODE_BURST_TX, tx));
-	burst_count_launch(false);
-	FI_POINT(FI_KERNEL);
-	return 0;
+	return burst_launched(false);
 }
 
 /* ---- the cipher under per-connection keys: the device cipher-key table ---- */
@@ -905,7 +866,7 @@ NET2_EXPORT int net2_packet_decrypt_burst_mc(
 	    kt, hashlen, (const uint8_t *)d_base, d_offsets, d_lens, n, d_seq,
 	    d_flags, (const uint8_t *)d_iv, d_result, (uint8_t *)d_out, d_plen,
 	    (hipStream_t)stream));
-	aes_count_launch(wave);
+	g_aes_launches.count(wave);
 	return 0;
 }
 

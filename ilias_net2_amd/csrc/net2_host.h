@@ -24,6 +24,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <atomic>
 #include <memory>
 
 #define NET2_EXPORT extern "C" __attribute__((visibility("default")))
@@ -296,6 +297,69 @@ bool dense_pinned(WorkPool &pool, const uint8_t *base, const uint64_t *off,
 void rebase_meta(WorkPool &pool, const uint64_t *off, const uint32_t *ln,
     uint64_t n, uint64_t rs, uint64_t *dst_off, uint32_t *dst_len);
 uint64_t var_chunk_packets(WorkPool &pool, const uint32_t *lens, uint64_t n);
+
+/* ---- form knobs and launch counters (net2_dgram.cpp) ---------------------- */
+
+/*
+ * A size threshold between two forms of a launch: what the C ABI set
+ * (set(v); v < 0 clears it), else the environment variable as it was at
+ * first use (A/B runs, one process per setting), else the caller's default.
+ * Relaxed atomics, no lock: a thread reading while another sets sees the old
+ * value or the new one.
+ */
+struct FormKnob {
+	const char *env_name;
+	std::atomic<int64_t> setting{-1};	/* -1: none */
+	std::atomic<int64_t> env{-2};		/* -2: not read yet; -1: not there */
+
+	void set(int64_t v)
+	{
+		setting.store(v < 0 ? -1 : v, std::memory_order_relaxed);
+	}
+	uint64_t get(uint64_t dflt)
+	{
+		uint64_t v;
+		return get(&v) ? v : dflt;
+	}
+	/* false: neither set nor in the environment -- the default holds, which
+	 * a caller whose default costs something works out only then */
+	bool get(uint64_t *v)
+	{
+		int64_t x = setting.load(std::memory_order_relaxed);
+		if (x < 0 && (x = env.load(std::memory_order_relaxed)) == -2) {
+			const char *e = getenv(env_name);
+			x = e != nullptr && *e != '\0' ?
+			    (int64_t)(strtoull(e, nullptr, 10) & INT64_MAX) : -1;
+			env.store(x, std::memory_order_relaxed);
+		}
+		if (x < 0)
+			return false;
+		*v = (uint64_t)x;
+		return true;
+	}
+};
+
+/* Launches by form (the *_stats calls). */
+struct FormCounts {
+	std::atomic<uint64_t> lane{0}, wave{0};
+
+	void count(bool is_wave)
+	{
+		(is_wave ? wave : lane).fetch_add(1, std::memory_order_relaxed);
+	}
+	void read(uint64_t *lanes, uint64_t *waves) const
+	{
+		if (lanes != nullptr)
+			*lanes = lane.load(std::memory_order_relaxed);
+		if (waves != nullptr)
+			*waves = wave.load(std::memory_order_relaxed);
+	}
+};
+
+/* The largest keyed hash burst that takes the wave form on the current
+ * device: net2_sha2_burst_limits' setting, else NET2_BURST_WAVE_MAX (0:
+ * never), else net2_burst_wave_default(). */
+uint64_t net2_burst_wave_max(void);
 
 /* ---- the burst steps (net2_dgram.cpp) ------------------------------------- */
 

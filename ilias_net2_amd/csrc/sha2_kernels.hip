@@ -22,6 +22,7 @@
  * prefetches block k+1 while compressing block k.
  */
 #include "sha2_device.h"
+#include "sha2_keyprep.h"
 #include "sha2_launch.h"
 
 #include <hip/hip_runtime.h>
@@ -31,6 +32,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <type_traits>
 
 namespace net2 {
 namespace dev {
@@ -636,12 +638,6 @@ __device__ __forceinline__ void digest_one(const uint8_t *p, uint32_t len,
 	finish<H, PADCONST>(p, len, (uint64_t)len << 3, kw, st);
 }
 
-/* Constant-pad schedule passed by value (kernarg -> SGPRs / LDS). */
-template <class W>
-struct PadKW {
-	W kw[sizeof(W) == 4 ? 64 : 80];
-};
-
 /* One lane of the fixed-stride layout: packet i. */
 template <class H, int AMODE, bool PADCONST, bool PREFETCH = H::PREFETCH>
 __device__ __forceinline__ void fixed_lane(uint64_t i,
@@ -951,20 +947,14 @@ __global__ __launch_bounds__(256) void var_kernel(const uint8_t *__restrict__ ba
  * over a whole batch under one connection key:
  *   HMAC(K, m) = H((K' ^ opad) || H((K' ^ ipad) || m)),  K' = K zero-padded.
  * The two key blocks -- the same for every packet of a launch -- are
- * compressed once on the host (hmac_midstates below) and arrive as kernel
- * arguments: the ipad / opad midstates, copied to LDS at kernel entry; every
- * lane hashes its packet from the inner midstate (bit count includes the key
+ * compressed once on the host (hmac_key_mids, sha2_keyprep.h) and arrive as
+ * a kernel argument (HMid): the ipad / opad midstates, copied to LDS at
+ * kernel entry; every lane hashes its packet from the inner midstate (bit count includes the key
  * block) and finishes with one outer compression over the inner digest.
  * (Until round 4 wave 0 of every workgroup compressed the key blocks while
  * the other waves waited: a second instance of the round code in the kernel,
  * which held the fixed-layout HMAC-SHA512 kernel at 115 VGPRs.)
  */
-struct HMid {
-	/* [0] K' ^ ipad, [1] K' ^ opad as digest words (SHA-256: 8 state words;
-	 * SHA-384/512: hi, lo of each 64-bit word); [2..3] the same for the
-	 * alternate rx key (HMAC_BURST_RX with rx.alt) */
-	uint32_t w[4][16];
-};
 
 /*
  * Where a lane's two midstates come from (hmac_lane's MIDS): inner() before
@@ -2939,155 +2929,6 @@ __global__ __launch_bounds__(256) void bin_ws_init_kernel(uint32_t *ws)
 		    __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-/* ---- host-side constant pad schedule ---------------------------------- */
-
-static inline uint32_t h_ror32(uint32_t x, int n)
-{
-	return (x >> n) | (x << (32 - n));
-}
-static inline uint64_t h_ror64(uint64_t x, int n)
-{
-	return (x >> n) | (x << (64 - n));
-}
-
-/* Pad block of a message whose length is a multiple of the block size. */
-static void pad_kw256(uint64_t bits, PadKW<uint32_t> &p)
-{
-	uint32_t w[64] = { 0 };
-	w[0] = 0x80000000u;
-	w[14] = (uint32_t)(bits >> 32);
-	w[15] = (uint32_t)bits;
-	for (int t = 16; t < 64; t++) {
-		uint32_t s0 = h_ror32(w[t - 15], 7) ^ h_ror32(w[t - 15], 18) ^
-		    (w[t - 15] >> 3);
-		uint32_t s1 = h_ror32(w[t - 2], 17) ^ h_ror32(w[t - 2], 19) ^
-		    (w[t - 2] >> 10);
-		w[t] = w[t - 16] + s0 + w[t - 7] + s1;
-	}
-	for (int t = 0; t < 64; t++)
-		p.kw[t] = K256[t] + w[t];
-}
-
-static void pad_kw512(uint64_t bits, PadKW<uint64_t> &p)
-{
-	uint64_t w[80] = { 0 };
-	w[0] = 0x8000000000000000ull;
-	w[15] = bits;	/* w[14] = high 64 bits of the 128-bit count = 0 */
-	for (int t = 16; t < 80; t++) {
-		uint64_t s0 = h_ror64(w[t - 15], 1) ^ h_ror64(w[t - 15], 8) ^
-		    (w[t - 15] >> 7);
-		uint64_t s1 = h_ror64(w[t - 2], 19) ^ h_ror64(w[t - 2], 61) ^
-		    (w[t - 2] >> 6);
-		w[t] = w[t - 16] + s0 + w[t - 7] + s1;
-	}
-	for (int t = 0; t < 80; t++)
-		p.kw[t] = K512[t] + w[t];
-}
-
-/*
- * The HMAC key blocks, once per launch on the host (RFC 2104 / FIPS 198-1:
- * the ipad and opad chaining values after one compression of K' ^ ipad /
- * K' ^ opad from the IV), in the word layout hmac_kernel's LDS copy takes.
- * One SHA-256 / SHA-512 compression each (FIPS 180-4 6.2.2 / 6.4.2, the
- * reference's SHA256Transform / SHA512Transform, src/sha2.c:374-445,
- * :663-734): product code of the launcher, not the test oracle.
- */
-static void h_compress256(uint32_t st[8], const uint32_t m[16])
-{
-	uint32_t w[64], v[8];
-	for (int t = 0; t < 16; t++)
-		w[t] = m[t];
-	for (int t = 16; t < 64; t++)
-		w[t] = w[t - 16] + (h_ror32(w[t - 15], 7) ^ h_ror32(w[t - 15], 18) ^
-		    (w[t - 15] >> 3)) + w[t - 7] + (h_ror32(w[t - 2], 17) ^
-		    h_ror32(w[t - 2], 19) ^ (w[t - 2] >> 10));
-	for (int i = 0; i < 8; i++)
-		v[i] = st[i];
-	for (int t = 0; t < 64; t++) {
-		const uint32_t t1 = v[7] + (h_ror32(v[4], 6) ^ h_ror32(v[4], 11) ^
-		    h_ror32(v[4], 25)) + ((v[4] & v[5]) ^ (~v[4] & v[6])) +
-		    K256[t] + w[t];
-		const uint32_t t2 = (h_ror32(v[0], 2) ^ h_ror32(v[0], 13) ^
-		    h_ror32(v[0], 22)) + ((v[0] & v[1]) ^ (v[0] & v[2]) ^
-		    (v[1] & v[2]));
-		for (int i = 7; i > 0; i--)
-			v[i] = v[i - 1];
-		v[4] += t1;
-		v[0] = t1 + t2;
-	}
-	for (int i = 0; i < 8; i++)
-		st[i] += v[i];
-}
-
-static void h_compress512(uint64_t st[8], const uint64_t m[16])
-{
-	uint64_t w[80], v[8];
-	for (int t = 0; t < 16; t++)
-		w[t] = m[t];
-	for (int t = 16; t < 80; t++)
-		w[t] = w[t - 16] + (h_ror64(w[t - 15], 1) ^ h_ror64(w[t - 15], 8) ^
-		    (w[t - 15] >> 7)) + w[t - 7] + (h_ror64(w[t - 2], 19) ^
-		    h_ror64(w[t - 2], 61) ^ (w[t - 2] >> 6));
-	for (int i = 0; i < 8; i++)
-		v[i] = st[i];
-	for (int t = 0; t < 80; t++) {
-		const uint64_t t1 = v[7] + (h_ror64(v[4], 14) ^ h_ror64(v[4], 18) ^
-		    h_ror64(v[4], 41)) + ((v[4] & v[5]) ^ (~v[4] & v[6])) +
-		    K512[t] + w[t];
-		const uint64_t t2 = (h_ror64(v[0], 28) ^ h_ror64(v[0], 34) ^
-		    h_ror64(v[0], 39)) + ((v[0] & v[1]) ^ (v[0] & v[2]) ^
-		    (v[1] & v[2]));
-		for (int i = 7; i > 0; i--)
-			v[i] = v[i - 1];
-		v[4] += t1;
-		v[0] = t1 + t2;
-	}
-	for (int i = 0; i < 8; i++)
-		st[i] += v[i];
-}
-
-/*
- * ipad / opad midstates of key block kb (K' zero-padded to the block, at
- * most 128 bytes) into hm->w[slot], hm->w[slot + 1].  halg: the SHA row
- * (1 SHA-256, 2 SHA-384, 3 SHA-512).
- */
-static void hmac_midstates(int halg, const uint8_t kb[128], HMid *hm,
-    int slot)
-{
-	for (int pass = 0; pass < 2; pass++) {
-		const uint8_t x = pass ? 0x5c : 0x36;
-		uint32_t *o = hm->w[slot + pass];
-		if (halg == 1) {
-			uint32_t st[8], m[16];
-			for (int i = 0; i < 8; i++)
-				st[i] = IV256[i];
-			for (int i = 0; i < 16; i++)
-				m[i] = (uint32_t)(kb[4 * i] ^ x) << 24 |
-				    (uint32_t)(kb[4 * i + 1] ^ x) << 16 |
-				    (uint32_t)(kb[4 * i + 2] ^ x) << 8 |
-				    (uint32_t)(kb[4 * i + 3] ^ x);
-			h_compress256(st, m);
-			for (int i = 0; i < 16; i++)
-				o[i] = i < 8 ? st[i] : 0u;
-		} else {
-			uint64_t st[8], m[16];
-			for (int i = 0; i < 8; i++)
-				st[i] = halg == 2 ? IV384[i] : IV512[i];
-			for (int i = 0; i < 16; i++) {
-				uint64_t v = 0;
-				for (int b = 0; b < 8; b++)
-					v = v << 8 | (uint8_t)(kb[8 * i + b] ^ x);
-				m[i] = v;
-			}
-			h_compress512(st, m);
-			for (int i = 0; i < 8; i++) {
-				o[2 * i] = (uint32_t)(st[i] >> 32);
-				o[2 * i + 1] = (uint32_t)st[i];
-			}
-		}
-	}
-}
-
 } /* namespace dev */
 } /* namespace net2 */
 
@@ -3252,18 +3093,65 @@ hipError_t net2_launch_var(int alg, const uint8_t *base,
 		    lens, ws, launch, n, out, dlen, is384);
 	return hipGetLastError();
 }
-/* Every mode takes H's pair loop.  (Until round 5 the SHA-256 VERIFY and
- * BURST_RX kernels dropped it: 1.5 % faster in round 1, when the key pass
- * held their VGPRs at 110.  With the midstates from the host they measured
- * +4.3 to +5.3 % (verify) and +2.9 to +3.3 % (burst RX) with it,
- * profiles/round5/ab_pairall_box*.txt.) */
 
+/* ---- the keyed launchers' dispatch -------------------------------------- */
+
+/* The hash of an HMAC row, as the keyed kernels' template arguments. */
+template <class H_, bool IS384_>
+struct HashSel {
+	typedef H_ H;
+	static constexpr bool IS384 = IS384_;
+};
+
+/* f(HashSel<H, IS384>{}) for SHA row halg (1..3) of an HMAC row.  (The
+ * fixed-layout HMAC takes Sha512HF: net2_launch_hmac's own case.) */
+template <class F>
+static void with_hash(int halg, F &&f)
+{
+	if (halg == NET2_ALG_SHA256)
+		f(HashSel<Sha256H, false>{});
+	else if (halg == NET2_ALG_SHA384)
+		f(HashSel<Sha512H, true>{});
+	else
+		f(HashSel<Sha512H, false>{});
+}
+
+/* f(std::integral_constant<int, MODE>{}) for burst mode HMAC_BURST_RX / _TX:
+ * MODE is the kernel family's RX or TX. */
+template <int RX, int TX, class F>
+static void with_burst_mode(int mode, F &&f)
+{
+	if (mode == HMAC_BURST_RX)
+		f(std::integral_constant<int, RX>{});
+	else
+		f(std::integral_constant<int, TX>{});
+}
+
+/* What the burst launchers check alike: an HMAC row and a burst mode, the
+ * offsets, counts the kernels' 32-bit indices hold, an IV a lane can hold
+ * and -- for the launchers over a key table (kt) -- the table. */
+static bool burst_launch_ok(int halg, int mode, const uint64_t *offsets,
+    uint64_t n, uint32_t ivlen, const KeyTabArgs *kt)
+{
+	return (mode == HMAC_BURST_RX || mode == HMAC_BURST_TX) &&
+	    halg >= NET2_ALG_SHA256 && halg <= NET2_ALG_SHA512 &&
+	    offsets != nullptr && n <= 0xffffffffu && ivlen <= 64 &&
+	    (kt == nullptr || (kt->conn != nullptr && kt->tab != nullptr &&
+	    kt->slots != 0));
+}
+
+/* The variable layout under one key.  Every mode takes H's pair loop.  (Until
+ * round 5 the SHA-256 VERIFY and BURST_RX kernels dropped it: 1.5 % faster
+ * in round 1, when the key pass held their VGPRs at 110.  With the midstates
+ * from the host they measured +4.3 to +5.3 % (verify) and +2.9 to +3.3 %
+ * (burst RX) with it, profiles/round5/ab_pairall_box*.txt.) */
 template <class H, bool IS384>
 static void launch_hmac_var_mode(int mode, unsigned grid, hipStream_t s,
     const uint8_t *base, const uint64_t *offsets, const uint32_t *lens,
     const uint32_t *ws, uint32_t launch, uint64_t n, uint8_t *out,
-    const HMid &hm, const PadKW<typename H::word> &pad, const BurstArgs &rx)
+    const HMid &hm, const BurstArgs &rx)
 {
+	const PadKW<typename H::word> pad = {};
 	if (mode == HMAC_SIGN)
 		hmac_kernel<H, false, HMAC_SIGN, IS384><<<grid, 256, 0, s>>>(base,
 		    offsets, lens, ws, launch, 0, 0, n, out, hm, pad, rx);
@@ -3285,25 +3173,33 @@ static void launch_hmac_var_mode(int mode, unsigned grid, hipStream_t s,
 
 /* The fixed layout (offsets == NULL): digests only. */
 template <class H, bool IS384>
-static void launch_hmac_fixed(bool padconst, unsigned grid, hipStream_t s,
-    const uint8_t *base, uint64_t stride, uint32_t fixed_len, uint64_t n,
-    uint8_t *out, const HMid &hm, const PadKW<typename H::word> &pad,
-    const BurstArgs &rx)
+static void launch_hmac_fixed(unsigned grid, hipStream_t s, const uint8_t *base,
+    uint64_t stride, uint32_t fixed_len, uint64_t n, uint8_t *out,
+    const HMid &hm, const BurstArgs &rx)
 {
-	if (padconst)
+	constexpr uint32_t blk = sizeof(typename H::word) * 16;
+	PadKW<typename H::word> pad = {};
+	if (fixed_len % blk == 0) {
+		const uint64_t ibits = ((uint64_t)fixed_len + blk) << 3;
+		if constexpr (sizeof(typename H::word) == 4)
+			pad_kw256(ibits, pad);
+		else
+			pad_kw512(ibits, pad);
 		hmac_kernel<H, true, HMAC_DIGESTS, IS384><<<grid, 256, 0, s>>>(
 		    base, nullptr, nullptr, nullptr, 0, stride, fixed_len, n, out,
 		    hm, pad, rx);
-	else
+	} else {
 		hmac_kernel<H, false, HMAC_DIGESTS, IS384><<<grid, 256, 0, s>>>(
 		    base, nullptr, nullptr, nullptr, 0, stride, fixed_len, n, out,
 		    hm, pad, rx);
+	}
 }
 
-hipError_t net2_launch_hmac(int alg, const uint8_t *key, size_t keylen,
-    const uint8_t *base, const uint64_t *offsets, const uint32_t *lens,
-    uint64_t stride, uint32_t fixed_len, uint64_t n, uint8_t *out,
-    uint32_t *ws, hipStream_t s, int mode, const BurstArgs *burst_args)
+hipError_t net2_launch_hmac(int alg, const uint8_t *key, const uint8_t *altkey,
+    size_t keylen, const uint8_t *base, const uint64_t *offsets,
+    const uint32_t *lens, uint64_t stride, uint32_t fixed_len, uint64_t n,
+    uint8_t *out, uint32_t *ws, hipStream_t s, int mode,
+    const BurstArgs *burst_args)
 {
 	if (mode != HMAC_DIGESTS && offsets == nullptr)
 		return hipErrorInvalidValue;	/* datagram modes: var layout */
@@ -3314,70 +3210,49 @@ hipError_t net2_launch_hmac(int alg, const uint8_t *key, size_t keylen,
 	    mode != HMAC_BURST_TX)
 		return hipErrorInvalidValue;
 	const BurstArgs rx = burst_args ? *burst_args : BurstArgs{};
+	/* the alternate key's bytes and the kernel's rx.alt go together */
+	if ((altkey != nullptr) != (mode == HMAC_BURST_RX && rx.alt != 0))
+		return hipErrorInvalidValue;
 	if (n == 0)
 		return hipSuccess;
 	const int halg = alg - 3;	/* HMAC row -> SHA row */
-	const bool s256 = halg == NET2_ALG_SHA256;
-	const int blk = s256 ? 64 : 128;
-	const bool is384 = halg == NET2_ALG_SHA384;
-	uint8_t kb[128] = { 0 };
-	if (keylen > (size_t)blk)
+	HMid hm;
+	if (!hmac_key_mids(halg, key, altkey, keylen, &hm))
 		return hipErrorInvalidValue;	/* registry keys are <= a block */
-	for (size_t i = 0; i < keylen; i++)
-		kb[i] = key[i];
-	HMid hm = {};
-	hmac_midstates(halg, kb, &hm, 0);
-	if (mode == HMAC_BURST_RX && rx.alt) {
-		uint8_t ab[128] = { 0 };
-		for (int i = 0; i < 32; i++)	/* K' as big-endian words */
-			for (int b = 0; b < 4; b++)
-				ab[4 * i + b] = (uint8_t)(rx.altkey[i] >> (24 - 8 * b));
-		hmac_midstates(halg, ab, &hm, 2);
-	}
+	hipError_t e = hipSuccess;
 	uint32_t launch = 0;
-	if (offsets != nullptr && ws != nullptr) {
-		hipError_t e = net2_bin_order(halg, lens, n, ws, s, &launch);
-		if (e != hipSuccess)
-			return e;
-	} else {
+	if (offsets != nullptr && ws != nullptr)
+		e = net2_bin_order(halg, lens, n, ws, s, &launch);
+	else
 		ws = nullptr;
+	if (e == hipSuccess) {
+		const unsigned grid = grid_for(n);
+		/* Sha256H serves both layouts; the fixed layout of the SHA-512
+		 * family has a hash shape of its own (Sha512HF).  (The order in
+		 * which the instances are first named here is their order in the
+		 * device code, and so part of the build id.) */
+		if (offsets != nullptr || halg == NET2_ALG_SHA256)
+			with_hash(halg, [&](auto h) {
+				typedef decltype(h) S;
+				if (offsets != nullptr)
+					launch_hmac_var_mode<typename S::H, S::IS384>(mode,
+					    grid, s, base, offsets, lens, ws, launch, n,
+					    out, hm, rx);
+				else if constexpr (std::is_same<typename S::H,
+				    Sha256H>::value)
+					launch_hmac_fixed<Sha256H, false>(grid, s, base,
+					    stride, fixed_len, n, out, hm, rx);
+			});
+		else if (halg == NET2_ALG_SHA384)
+			launch_hmac_fixed<Sha512HF, true>(grid, s, base, stride,
+			    fixed_len, n, out, hm, rx);
+		else
+			launch_hmac_fixed<Sha512HF, false>(grid, s, base, stride,
+			    fixed_len, n, out, hm, rx);
+		e = hipGetLastError();
 	}
-	const unsigned grid = grid_for(n);
-	const bool padconst = offsets == nullptr && fixed_len % blk == 0;
-	const uint64_t ibits = ((uint64_t)fixed_len + blk) << 3;
-	if (s256) {
-		PadKW<uint32_t> pad = {};
-		if (offsets != nullptr) {
-			launch_hmac_var_mode<Sha256H, false>(mode, grid, s, base,
-			    offsets, lens, ws, launch, n, out, hm, pad, rx);
-		} else {
-			if (padconst)
-				pad_kw256(ibits, pad);
-			launch_hmac_fixed<Sha256H, false>(padconst, grid, s, base,
-			    stride, fixed_len, n, out, hm, pad, rx);
-		}
-	} else {
-		PadKW<uint64_t> pad = {};
-		if (offsets != nullptr) {
-			if (is384)
-				launch_hmac_var_mode<Sha512H, true>(mode, grid, s, base,
-				    offsets, lens, ws, launch, n, out, hm, pad, rx);
-			else
-				launch_hmac_var_mode<Sha512H, false>(mode, grid, s,
-				    base, offsets, lens, ws, launch, n, out, hm, pad,
-				    rx);
-		} else {
-			if (padconst)
-				pad_kw512(ibits, pad);
-			if (is384)
-				launch_hmac_fixed<Sha512HF, true>(padconst, grid, s,
-				    base, stride, fixed_len, n, out, hm, pad, rx);
-			else
-				launch_hmac_fixed<Sha512HF, false>(padconst, grid, s,
-				    base, stride, fixed_len, n, out, hm, pad, rx);
-		}
-	}
-	return hipGetLastError();
+	key_wipe(&hm, sizeof(hm));
+	return e;
 }
 
 hipError_t net2_launch_keytab_set(int alg, Net2KeyEnt *ent, uint32_t side,
@@ -3386,42 +3261,15 @@ hipError_t net2_launch_keytab_set(int alg, Net2KeyEnt *ent, uint32_t side,
 {
 	const int halg = alg - 3;	/* HMAC row -> SHA row */
 	if (halg < NET2_ALG_SHA256 || halg > NET2_ALG_SHA512 || ent == nullptr ||
-	    keylen > (size_t)(halg == NET2_ALG_SHA256 ? 64 : 128))
+	    (side != 0 && key == nullptr))
 		return hipErrorInvalidValue;
 	HMid hm = {};
-	if (side != 0) {
-		uint8_t kb[128] = { 0 };
-		if (key == nullptr)
-			return hipErrorInvalidValue;
-		for (size_t i = 0; i < keylen; i++)
-			kb[i] = key[i];
-		hmac_midstates(halg, kb, &hm, 0);
-		if (side == NET2_KT_RX && altkey != nullptr) {
-			uint8_t ab[128] = { 0 };
-			for (size_t i = 0; i < keylen; i++)
-				ab[i] = altkey[i];
-			hmac_midstates(halg, ab, &hm, 2);
-		}
-	}
+	if (side != 0 && !hmac_key_mids(halg, key,
+	    side == NET2_KT_RX ? altkey : nullptr, keylen, &hm))
+		return hipErrorInvalidValue;
 	keytab_set_kernel<<<1, 64, 0, s>>>(ent, side, bits, cutoff, rx_start, hm);
+	key_wipe(&hm, sizeof(hm));
 	return hipGetLastError();
-}
-
-template <class H, bool IS384>
-static void launch_hmac_mc(int mode, unsigned grid, hipStream_t s,
-    const uint8_t *base, const uint64_t *offsets, const uint32_t *lens,
-    const uint32_t *ws, uint32_t launch, uint64_t n, uint8_t *out,
-    const KeyTabArgs &kt, const BurstArgs &rx)
-{
-	const PadKW<typename H::word> pad = {};
-	if (mode == HMAC_BURST_RX)
-		hmac_mc_kernel<H, HMAC_BURST_RX_MC, IS384><<<grid, 256, 0, s>>>(
-		    base, offsets, lens, ws, launch, n, out, kt.conn, kt.tab,
-		    kt.slots, pad, rx);
-	else
-		hmac_mc_kernel<H, HMAC_BURST_TX_MC, IS384><<<grid, 256, 0, s>>>(
-		    base, offsets, lens, ws, launch, n, out, kt.conn, kt.tab,
-		    kt.slots, pad, rx);
 }
 
 hipError_t net2_launch_hmac_mc(int alg, const KeyTabArgs &kt,
@@ -3430,10 +3278,7 @@ hipError_t net2_launch_hmac_mc(int alg, const KeyTabArgs &kt,
     const BurstArgs &args)
 {
 	const int halg = alg - 3;	/* HMAC row -> SHA row */
-	if ((mode != HMAC_BURST_RX && mode != HMAC_BURST_TX) ||
-	    halg < NET2_ALG_SHA256 || halg > NET2_ALG_SHA512 ||
-	    offsets == nullptr || kt.conn == nullptr || kt.tab == nullptr ||
-	    kt.slots == 0 || args.rec != nullptr)
+	if (!burst_launch_ok(halg, mode, offsets, n, 0, &kt) || args.rec != nullptr)
 		return hipErrorInvalidValue;
 	if (n == 0)
 		return hipSuccess;
@@ -3444,31 +3289,16 @@ hipError_t net2_launch_hmac_mc(int alg, const KeyTabArgs &kt,
 			return e;
 	}
 	const unsigned grid = grid_for(n);
-	if (halg == NET2_ALG_SHA256)
-		launch_hmac_mc<Sha256H, false>(mode, grid, s, base, offsets, lens,
-		    ws, launch, n, out, kt, args);
-	else if (halg == NET2_ALG_SHA384)
-		launch_hmac_mc<Sha512H, true>(mode, grid, s, base, offsets, lens,
-		    ws, launch, n, out, kt, args);
-	else
-		launch_hmac_mc<Sha512H, false>(mode, grid, s, base, offsets, lens,
-		    ws, launch, n, out, kt, args);
+	with_hash(halg, [&](auto h) {
+		typedef decltype(h) S;
+		const PadKW<typename S::H::word> pad = {};
+		with_burst_mode<HMAC_BURST_RX_MC, HMAC_BURST_TX_MC>(mode, [&](auto m) {
+			hmac_mc_kernel<typename S::H, decltype(m)::value, S::IS384>
+			    <<<grid, 256, 0, s>>>(base, offsets, lens, ws, launch, n,
+			    out, kt.conn, kt.tab, kt.slots, pad, args);
+		});
+	});
 	return hipGetLastError();
-}
-
-template <class H, bool IS384>
-static void launch_burst_wave(int mode, uint64_t n, uint32_t G, hipStream_t s,
-    const uint8_t *base, const uint64_t *offsets, const uint32_t *lens,
-    const HMid &hm, const BurstArgs &a, uint8_t *result, uint8_t *iv,
-    uint32_t ivlen, uint8_t *out)
-{
-	const unsigned grid = (unsigned)((n + G - 1) / G);
-	if (mode == HMAC_BURST_RX)
-		burst_wave_kernel<H, HMAC_BURST_RX, IS384><<<grid, 128, 0, s>>>(
-		    base, offsets, lens, n, G, hm, a, result, iv, ivlen, out);
-	else
-		burst_wave_kernel<H, HMAC_BURST_TX, IS384><<<grid, 128, 0, s>>>(
-		    base, offsets, lens, n, G, hm, a, result, iv, ivlen, out);
 }
 
 /* SIMDs of the current device (0: unknown), cached per ordinal. */
@@ -3502,89 +3332,45 @@ static uint32_t burst_wave_group(uint64_t n)
 	    std::max<uint64_t>(1, (n + simds - 1) / simds));
 }
 
-/* net2_sha2_burst_limits' setting (-1: none) */
-static std::atomic<int64_t> g_burst_wave_max{-1};
-
-void net2_set_burst_wave_max(int64_t v)
+uint64_t net2_burst_wave_default(void)
 {
-	g_burst_wave_max.store(v < 0 ? -1 : v, std::memory_order_relaxed);
-}
-
-uint64_t net2_burst_wave_max(void)
-{
-	const int64_t set = g_burst_wave_max.load(std::memory_order_relaxed);
-	if (set >= 0)
-		return (uint64_t)set;
-	/* NET2_BURST_WAVE_MAX, read once (A/B runs, one process per setting) */
-	static const int64_t env = [] {
-		const char *e = getenv("NET2_BURST_WAVE_MAX");
-		return e != nullptr && *e != '\0' ?
-		    (int64_t)(strtoull(e, nullptr, 10) & INT64_MAX) : (int64_t)-1;
-	}();
-	if (env >= 0)
-		return (uint64_t)env;
 	/* BW_GMAX datagrams per SIMD: beyond that a pass of the wave form
 	 * expands too few blocks per datagram to beat the lane form */
 	return device_simds() * BW_GMAX;
 }
 
-hipError_t net2_launch_burst_wave(int alg, const uint8_t *key, size_t keylen,
-    const uint8_t *base, const uint64_t *offsets, const uint32_t *lens,
-    uint64_t n, const BurstArgs *args, uint8_t *result, uint8_t *iv,
-    uint32_t ivlen, uint8_t *out, int mode, hipStream_t s)
+hipError_t net2_launch_burst_wave(int alg, const uint8_t *key,
+    const uint8_t *altkey, size_t keylen, const uint8_t *base,
+    const uint64_t *offsets, const uint32_t *lens, uint64_t n,
+    const BurstArgs *args, uint8_t *result, uint8_t *iv, uint32_t ivlen,
+    uint8_t *out, int mode, hipStream_t s)
 {
-	if ((mode != HMAC_BURST_RX && mode != HMAC_BURST_TX) || args == nullptr ||
-	    offsets == nullptr || ivlen > 64 || n > 0xffffffffu)
+	const int halg = alg - 3;	/* HMAC row -> SHA row */
+	if (!burst_launch_ok(halg, mode, offsets, n, ivlen, nullptr) ||
+	    args == nullptr)
 		return hipErrorInvalidValue;
 	if (mode == HMAC_BURST_RX && args->rec != nullptr)
 		return hipErrorInvalidValue;
+	/* the alternate key's bytes and the kernel's args->alt go together */
+	if ((altkey != nullptr) != (mode == HMAC_BURST_RX && args->alt != 0))
+		return hipErrorInvalidValue;
 	if (n == 0)
 		return hipSuccess;
-	const int halg = alg - 3;	/* HMAC row -> SHA row */
-	const int blk = halg == NET2_ALG_SHA256 ? 64 : 128;
-	if (halg < NET2_ALG_SHA256 || halg > NET2_ALG_SHA512 ||
-	    keylen > (size_t)blk)
+	HMid hm;
+	if (!hmac_key_mids(halg, key, altkey, keylen, &hm))
 		return hipErrorInvalidValue;
-	uint8_t kb[128] = { 0 };
-	for (size_t j = 0; j < keylen; j++)
-		kb[j] = key[j];
-	HMid hm = {};
-	hmac_midstates(halg, kb, &hm, 0);
-	if (mode == HMAC_BURST_RX && args->alt) {
-		uint8_t ab[128] = { 0 };
-		for (int j = 0; j < 32; j++)	/* K' as big-endian words */
-			for (int b = 0; b < 4; b++)
-				ab[4 * j + b] = (uint8_t)(args->altkey[j] >> (24 - 8 * b));
-		hmac_midstates(halg, ab, &hm, 2);
-	}
 	const uint32_t G = burst_wave_group(n);
-	if (halg == NET2_ALG_SHA256)
-		launch_burst_wave<Sha256H, false>(mode, n, G, s, base, offsets,
-		    lens, hm, *args, result, iv, ivlen, out);
-	else if (halg == NET2_ALG_SHA384)
-		launch_burst_wave<Sha512H, true>(mode, n, G, s, base, offsets,
-		    lens, hm, *args, result, iv, ivlen, out);
-	else
-		launch_burst_wave<Sha512H, false>(mode, n, G, s, base, offsets,
-		    lens, hm, *args, result, iv, ivlen, out);
-	return hipGetLastError();
-}
-
-template <class H, bool IS384>
-static void launch_burst_wave_mc(int mode, uint64_t n, uint32_t G, hipStream_t s,
-    const uint8_t *base, const uint64_t *offsets, const uint32_t *lens,
-    const KeyTabArgs &kt, const BurstArgs &a, uint8_t *result, uint8_t *iv,
-    uint32_t ivlen, uint8_t *out)
-{
 	const unsigned grid = (unsigned)((n + G - 1) / G);
-	if (mode == HMAC_BURST_RX)
-		burst_wave_mc_kernel<H, HMAC_BURST_RX_MC, IS384><<<grid, 128, 0, s>>>(
-		    base, offsets, lens, n, G, kt.conn, kt.tab, kt.slots, a.seq,
-		    a.flags, result, iv, ivlen, out);
-	else
-		burst_wave_mc_kernel<H, HMAC_BURST_TX_MC, IS384><<<grid, 128, 0, s>>>(
-		    base, offsets, lens, n, G, kt.conn, kt.tab, kt.slots, a.seq,
-		    a.flags, result, iv, ivlen, out);
+	with_hash(halg, [&](auto h) {
+		typedef decltype(h) S;
+		with_burst_mode<HMAC_BURST_RX, HMAC_BURST_TX>(mode, [&](auto m) {
+			burst_wave_kernel<typename S::H, decltype(m)::value, S::IS384>
+			    <<<grid, 128, 0, s>>>(base, offsets, lens, n, G, hm,
+			    *args, result, iv, ivlen, out);
+		});
+	});
+	key_wipe(&hm, sizeof(hm));
+	return hipGetLastError();
 }
 
 hipError_t net2_launch_burst_wave_mc(int alg, const KeyTabArgs &kt,
@@ -3593,11 +3379,8 @@ hipError_t net2_launch_burst_wave_mc(int alg, const KeyTabArgs &kt,
     uint32_t ivlen, uint8_t *out, int mode, hipStream_t s)
 {
 	const int halg = alg - 3;	/* HMAC row -> SHA row */
-	if ((mode != HMAC_BURST_RX && mode != HMAC_BURST_TX) ||
-	    halg < NET2_ALG_SHA256 || halg > NET2_ALG_SHA512 ||
-	    offsets == nullptr || kt.conn == nullptr || kt.tab == nullptr ||
-	    kt.slots == 0 || args.rec != nullptr || result == nullptr ||
-	    ivlen > 64 || n > 0xffffffffu)
+	if (!burst_launch_ok(halg, mode, offsets, n, ivlen, &kt) ||
+	    args.rec != nullptr || result == nullptr)
 		return hipErrorInvalidValue;
 	/* RX: the decoded headers to both arrays or to neither; TX: both are
 	 * the inputs, and the sealed datagrams need somewhere to go */
@@ -3607,15 +3390,16 @@ hipError_t net2_launch_burst_wave_mc(int alg, const KeyTabArgs &kt,
 	if (n == 0)
 		return hipSuccess;
 	const uint32_t G = burst_wave_group(n);
-	if (halg == NET2_ALG_SHA256)
-		launch_burst_wave_mc<Sha256H, false>(mode, n, G, s, base, offsets,
-		    lens, kt, args, result, iv, ivlen, out);
-	else if (halg == NET2_ALG_SHA384)
-		launch_burst_wave_mc<Sha512H, true>(mode, n, G, s, base, offsets,
-		    lens, kt, args, result, iv, ivlen, out);
-	else
-		launch_burst_wave_mc<Sha512H, false>(mode, n, G, s, base, offsets,
-		    lens, kt, args, result, iv, ivlen, out);
+	const unsigned grid = (unsigned)((n + G - 1) / G);
+	with_hash(halg, [&](auto h) {
+		typedef decltype(h) S;
+		with_burst_mode<HMAC_BURST_RX_MC, HMAC_BURST_TX_MC>(mode, [&](auto m) {
+			burst_wave_mc_kernel<typename S::H, decltype(m)::value, S::IS384>
+			    <<<grid, 128, 0, s>>>(base, offsets, lens, n, G, kt.conn,
+			    kt.tab, kt.slots, args.seq, args.flags, result, iv, ivlen,
+			    out);
+		});
+	});
 	return hipGetLastError();
 }
 

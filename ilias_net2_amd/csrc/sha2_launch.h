@@ -7,6 +7,7 @@
 #define NET2_SHA2_LAUNCH_H
 
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 /* Registry indices, shared with include/net2/hash.h. */
@@ -114,8 +115,12 @@ struct BurstArgs {
 	int alt_enc_set;
 	int no_cutoff;
 	uint32_t cutoff, rx_start;
-	uint32_t altkey[32];	/* K' as big-endian words (the launcher turns
-				 * it into midstates; unused by the kernel) */
+	/* Unused and left zero: no key material travels here (the alternate
+	 * key reaches a launcher as bytes, the kernel as midstates).  The slot
+	 * stays because taking it out moves the kernel arguments of every
+	 * hmac_kernel and burst_wave_kernel instance, which a change that does
+	 * so has to measure. */
+	uint32_t unused_pad[32];
 	/* TX: when set, the datagrams in base are left as they are and the
 	 * lane at binned position g writes rec + g * (hashlen + 16): the hash
 	 * field (hashlen bytes, when OK), then uint32 header words as on the
@@ -123,11 +128,16 @@ struct BurstArgs {
 	 * then not written (the host burst path) */
 	uint8_t *rec;
 };
-hipError_t net2_launch_hmac(int alg, const uint8_t *key, size_t keylen,
-    const uint8_t *base, const uint64_t *offsets, const uint32_t *lens,
-    uint64_t stride, uint32_t fixed_len, uint64_t n, uint8_t *out,
-    uint32_t *ws, hipStream_t s, int mode = NET2_HMAC_MODE_DIGESTS,
-    const BurstArgs *burst_args = nullptr);
+/* (the layout every keyed kernel's arguments were built and measured with) */
+static_assert(sizeof(BurstArgs) == 184 && offsetof(BurstArgs, rec) == 176,
+    "BurstArgs is a kernel argument: its layout is fixed");
+/* altkey (BURST_RX with burst_args->alt, else NULL): the alternate rx key,
+ * keylen bytes as key */
+hipError_t net2_launch_hmac(int alg, const uint8_t *key, const uint8_t *altkey,
+    size_t keylen, const uint8_t *base, const uint64_t *offsets,
+    const uint32_t *lens, uint64_t stride, uint32_t fixed_len, uint64_t n,
+    uint8_t *out, uint32_t *ws, hipStream_t s,
+    int mode = NET2_HMAC_MODE_DIGESTS, const BurstArgs *burst_args = nullptr);
 
 /*
  * Device key table (net2_burst_keytab, include/net2/packet.h): one entry per
@@ -200,12 +210,14 @@ hipError_t net2_launch_hmac_mc(int alg, const KeyTabArgs &kt,
  * either may be NULL together; TX: the inputs, and rec).  result: the final
  * code per datagram (RX; TX without rec); iv: RX IVs (ivlen <= 64; NULL or
  * 0: none); out: TX without rec, the datagrams sealed in place (== base).
- * No workspace, no separate fold / IV launch.
+ * No workspace, no separate fold / IV launch.  altkey as for
+ * net2_launch_hmac.
  */
-hipError_t net2_launch_burst_wave(int alg, const uint8_t *key, size_t keylen,
-    const uint8_t *base, const uint64_t *offsets, const uint32_t *lens,
-    uint64_t n, const BurstArgs *args, uint8_t *result, uint8_t *iv,
-    uint32_t ivlen, uint8_t *out, int mode, hipStream_t s);
+hipError_t net2_launch_burst_wave(int alg, const uint8_t *key,
+    const uint8_t *altkey, size_t keylen, const uint8_t *base,
+    const uint64_t *offsets, const uint32_t *lens, uint64_t n,
+    const BurstArgs *args, uint8_t *result, uint8_t *iv, uint32_t ivlen,
+    uint8_t *out, int mode, hipStream_t s);
 /*
  * The same for bursts over many connections
  * (net2_packet_{decode,encode}_burst_mc, burst_wave_mc_kernel): the keys of
@@ -220,12 +232,10 @@ hipError_t net2_launch_burst_wave_mc(int alg, const KeyTabArgs &kt,
     const uint8_t *base, const uint64_t *offsets, const uint32_t *lens,
     uint64_t n, const BurstArgs &args, uint8_t *result, uint8_t *iv,
     uint32_t ivlen, uint8_t *out, int mode, hipStream_t s);
-/* The largest burst the two wave launchers are for on the current device:
- * 16 datagrams per SIMD, unless net2_sha2_burst_limits set a limit
- * (net2_set_burst_wave_max; < 0 clears it) or NET2_BURST_WAVE_MAX was in
- * the environment at first use (0: never). */
-uint64_t net2_burst_wave_max(void);
-void net2_set_burst_wave_max(int64_t v);
+/* The largest burst the two wave launchers are for on the current device
+ * by default: 16 datagrams per SIMD (net2_burst_wave_max, net2_host.h, is
+ * the limit in force). */
+uint64_t net2_burst_wave_default(void);
 
 /*
  * Coalesced small jobs (sha2_coalesce.cpp): many independent requests from
