@@ -22,7 +22,7 @@
 
 /*
  * Binning workspace (uint32 words): a 16-word header (the one-pass
- * binning's state, sha2_kernels.hip bin_onepass_kernel), the histogram in
+ * binning's state, sha2_bin.h bin_onepass_kernel), the histogram in
  * two parities (2 x NBINS), the barrier words (2 x NBINS, two parities and
  * the probe stamps), then perm[n].  Header words:
  */
@@ -269,7 +269,7 @@ hipError_t net2_launch_jobs(const uint8_t *stage, const Net2Job *jobs,
 /*
  * Packet bursts (net2_packet_{encode,decode}_burst): per-datagram header
  * bookkeeping (prep) and the fold of HMAC verdicts + IV derivation (final);
- * see sha2_kernels.hip.
+ * see sha2_burst.h.
  */
 hipError_t net2_launch_burst_prep(uint8_t *base, const uint64_t *offsets,
     const uint32_t *lens, uint64_t n, int encode, int hash_set, int enc_set,

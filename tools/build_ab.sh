@@ -1,7 +1,8 @@
 #!/bin/bash
 # Build an A/B variant of libnet2_sha2.so: tools/ab/<name>.so from
-# sha2_kernels.hip compiled with the given -D flags, linked with the
-# in-tree host objects (make -C ilias_net2_amd/csrc first).
+# sha2_kernels.hip (and the sha2_*.h family headers it includes) compiled
+# with the given -D flags, linked with the in-tree host objects and the
+# cipher kernels' object (make -C ilias_net2_amd/csrc first).
 #   tools/build_ab.sh a1pf0 -DNET2_VAR_A1_PREFETCH=0
 set -eu
 name=$1; shift
@@ -19,6 +20,6 @@ ID=$(sha256sum $HERE/ab/$name.fatbin | cut -c1-16)
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $HERE/ab/$name.so \
     $HERE/ab/$name.o $HERE/ab/$name.bid.o $SRC/build/net2_runtime.o $SRC/build/net2_batch.o \
     $SRC/build/net2_single.o $SRC/build/net2_dgram.o $SRC/build/net2_burst_host.o \
-    $SRC/build/sha2_coalesce.o $SRC/build/sha2_stream.o -lpthread
+    $SRC/build/sha2_coalesce.o $SRC/build/sha2_stream.o $SRC/build/aes_kernels_ld.o -lpthread
 rm -f $HERE/ab/$name.o $HERE/ab/$name.bid.o $HERE/ab/$name.fatbin
 echo built $HERE/ab/$name.so "(build id $ID)"

@@ -1,10 +1,9 @@
 // kernel_ab.hip -- launch-shape A/B of the shipped SHA-256 fixed kernel body
 // on the config-2 workload (1M x 1 KiB, device-resident).  All variants run
-// the same lane code (fixed_lane from sha2_kernels.hip); only block size,
+// the same lane code (fixed_lane from sha2_digest.h); only block size,
 // register attributes and grid shape differ.  Outputs are compared.
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -I ilias_net2_amd/csrc tools/kernel_ab.hip -o tools/kernel_ab
-#define NET2_SHA2_NO_LAUNCHERS
-#include "../ilias_net2_amd/csrc/sha2_kernels.hip"
+#include "../ilias_net2_amd/csrc/sha2_digest.h"
 
 #include <algorithm>
 #include <cstdio>
