@@ -10,6 +10,14 @@
  * share the block code (aes_device.h) and the tests.  Small RX bursts take
  * the wave form instead (one wave per datagram, further down).
  *
+ * What a lane does with its datagram -- the burst's arguments, the prep step
+ * that settles what needs no cipher, the CBC chain of each direction, the
+ * connection checks of the _mc calls -- is aes_cbc.h, host and device code
+ * that the host tests run as it stands.  This file keeps what is device-only:
+ * the LDS table and the round-key accessors, the ranking, the kernels (each
+ * lane kernel: prep, rank, table, one call of its direction's chain under its
+ * key source), the wave form, the table update and the launchers.
+ *
  * LDS layout.  A workgroup is 256 lanes and holds one T-table (Te0 forward,
  * Td0 inverse) replicated 32 times: entry x for lane l is dword
  * x * 32 + (l & 31), 32 KiB.  A ds_read_b32 is served per half-wave of 32
@@ -34,6 +42,7 @@
  * access mode of gfx9+ global memory that the hash kernels rely on as well).
  * A lane touches only bytes of its own datagram's payload.
  */
+#include "aes_cbc.h"
 #include "aes_device.h"
 #include "aes_launch.h"
 #include "aes_sched.h"
@@ -45,11 +54,6 @@
 #include <string.h>
 
 namespace {
-
-constexpr uint32_t PKT_HDR = 8;			/* net2_ph_overhead */
-constexpr uint32_t PKT_PH_ENCRYPTED = 0x00000001u;
-constexpr uint32_t PKT_PH_SIGNED = 0x00000002u;
-constexpr uint8_t PKT_OK = 0, PKT_RESOURCE = 1, PKT_BAD = 2;
 
 constexpr int AES_WG = 256;		/* lanes per workgroup = table entries */
 /* copies of the table: one per bank (-DNET2_AES_REP=1, a power of two: the
@@ -68,46 +72,7 @@ struct AesKeys {
 	AesSched k[NK];
 };
 
-struct AesBurstArgs {
-	const uint8_t *in;	/* decrypt: the burst; encrypt: unused */
-	uint8_t *out;		/* decrypt: d_out; encrypt: the burst */
-	const uint64_t *offsets;
-	const uint32_t *lens;
-	const uint32_t *seq;	/* decrypt with an alternate key */
-	const uint32_t *flags;
-	const uint8_t *iv;
-	uint8_t *result;
-	uint32_t *plen;		/* decrypt: out; encrypt: in */
-	uint32_t *wire_len;	/* encrypt */
-	uint64_t n;
-	uint32_t hashlen;
-	uint32_t no_cutoff, cutoff, rx_start;
-};
-
 /* ---- device ------------------------------------------------------------------ */
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-/* A block at any byte alignment <-> four big-endian words. */
-__device__ __forceinline__ void ld16(const uint8_t *p, uint32_t (&w)[4])
-{
-	u32x4 v;
-	__builtin_memcpy(&v, p, 16);
-	w[0] = __builtin_bswap32(v.x);
-	w[1] = __builtin_bswap32(v.y);
-	w[2] = __builtin_bswap32(v.z);
-	w[3] = __builtin_bswap32(v.w);
-}
-
-__device__ __forceinline__ void st16(uint8_t *p, const uint32_t (&w)[4])
-{
-	u32x4 v;
-	v.x = __builtin_bswap32(w[0]);
-	v.y = __builtin_bswap32(w[1]);
-	v.z = __builtin_bswap32(w[2]);
-	v.w = __builtin_bswap32(w[3]);
-	__builtin_memcpy(p, &v, 16);
-}
 
 /* The lane's copy of the replicated table: entry x at p[x * 32]. */
 struct LdsTab {
@@ -148,9 +113,28 @@ __device__ __forceinline__ void aes_build_table(uint32_t *tab)
 	__syncthreads();
 }
 
-__device__ __forceinline__ uint32_t payload_at(uint32_t fl, uint32_t hashlen)
+/*
+ * With an alternate rx key the choice is per datagram: the launch's two
+ * schedules go to LDS (lanes 0..59 the active one, 64..123 the alternate one;
+ * published by the table build's barrier) and a datagram's pick is an address
+ * there (net2_ck_rx_key, src/conn_keys.c:447-476, as the HMAC step chose).
+ */
+__device__ __forceinline__ void stage_rx_keys(uint32_t *rks,
+    const AesKeys<2> &keys)
 {
-	return PKT_HDR + ((fl & PKT_PH_SIGNED) != 0 ? hashlen : 0u);
+	const uint32_t t = threadIdx.x;
+	if (t < NET2_AES_RKWORDS)
+		rks[t] = keys.k[0].w[t];
+	else if (t >= 64 && t < 64 + NET2_AES_RKWORDS)
+		rks[AES_RK_STRIDE + t - 64] = keys.k[1].w[t - 64];
+}
+
+__device__ __forceinline__ const uint32_t *staged_rx_key(const uint32_t *rks,
+    const AesBurstArgs &a, uint64_t i, uint32_t fl)
+{
+	const bool alt = aes_rx_alt(true, a.no_cutoff != 0, fl, a.seq[i], a.cutoff,
+	    a.rx_start);
+	return rks + (alt ? AES_RK_STRIDE : 0);
 }
 
 /*
@@ -187,37 +171,12 @@ __device__ __forceinline__ uint32_t lanes_by_work(uint32_t *scratch,
 }
 
 /*
- * RX.  Only a datagram that arrives OK with PH_ENCRYPTED is decrypted; every
- * other one keeps its code, gets plen 0 and is not touched.  The last block
- * goes first: its padding decides whether the datagram is BAD (as is an empty
- * or ragged ciphertext), and a BAD datagram is not written at all.  Then the
- * blocks in order, the next one's ciphertext loaded before the current one is
- * decrypted; in place, a block is overwritten only after it and its
- * predecessor's ciphertext are in registers.
+ * The lane kernels.  Each is four steps: the prep of the datagram in the
+ * lane's own position (aes_cbc.h: what needs no cipher is settled there), the
+ * ranking, the table, then the direction's one chain (cbc_decrypt_lane /
+ * cbc_encrypt_lane, aes_cbc.h) for the datagram the lane drew, under the
+ * kernel's key source.
  */
-
-/* Datagram i's ciphertext blocks; what needs no cipher is settled here. */
-__device__ __forceinline__ uint32_t decrypt_prep(const AesBurstArgs &a,
-    uint64_t i)
-{
-	if (i >= a.n)
-		return 0;
-	const uint32_t fl = a.flags[i];
-	uint32_t nb = 0;
-	if (a.result[i] == PKT_OK && (fl & PKT_PH_ENCRYPTED) != 0) {
-		const uint32_t po = payload_at(fl, a.hashlen);
-		const uint32_t len = a.lens[i];
-		const uint32_t clen = len > po ? len - po : 0u;
-		if (clen != 0 && (clen & 15u) == 0)
-			nb = clen >> 4;
-		else
-			a.result[i] = PKT_BAD;
-	}
-	if (nb == 0)
-		a.plen[i] = 0;
-	return nb;
-}
-
 template <bool ALT>
 __global__ __launch_bounds__(AES_WG) void aes_cbc_decrypt_kernel(
     const AesBurstArgs a, const AesKeys<ALT ? 2 : 1> keys)
@@ -227,13 +186,8 @@ __global__ __launch_bounds__(AES_WG) void aes_cbc_decrypt_kernel(
 	__shared__ __attribute__((aligned(16))) uint32_t
 	    rks[ALT ? 2 * AES_RK_STRIDE : 4];
 
-	if (ALT) {
-		const uint32_t t = threadIdx.x;
-		if (t < NET2_AES_RKWORDS)
-			rks[t] = keys.k[0].w[t];
-		else if (t >= 64 && t < 64 + NET2_AES_RKWORDS)
-			rks[AES_RK_STRIDE + t - 64] = keys.k[ALT ? 1 : 0].w[t - 64];
-	}
+	if constexpr (ALT)
+		stage_rx_keys(rks, keys);
 	const uint64_t first = (uint64_t)blockIdx.x * AES_WG;
 	uint32_t nb;
 	const uint64_t i = first + lanes_by_work(tab,
@@ -243,88 +197,14 @@ __global__ __launch_bounds__(AES_WG) void aes_cbc_decrypt_kernel(
 		return;
 
 	const uint32_t fl = a.flags[i];
-	const uint32_t po = payload_at(fl, a.hashlen);
 	const LdsTab T = { tab + (threadIdx.x & (AES_REP - 1)) };
-	/* net2_ck_rx_key (src/conn_keys.c:447-476), as the HMAC step chose */
-	const bool alt = ALT && aes_rx_alt(true, a.no_cutoff != 0, fl, a.seq[i],
-	    a.cutoff, a.rx_start);
-	const RkLds KL = { rks + (alt ? AES_RK_STRIDE : 0) };
-	const RkArgs KA = { keys.k[0] };
-	const uint64_t off = a.offsets[i] + po;
-	const uint8_t *src = a.in + off;
-	uint8_t *dst = a.out + off;
-	uint32_t ivw[4], c[4], prev[4];
-	uint32_t b = nb - 1, pad = 0;
-
-	ld16(a.iv + NET2_AES_BLOCK * i, ivw);
-	ld16(src + 16 * (uint64_t)b, c);
-	if (nb > 1) {
-		ld16(src + 16 * (uint64_t)(b - 1), prev);
+	if constexpr (ALT) {
+		const RkLds K = { staged_rx_key(rks, a, i, fl) };
+		cbc_decrypt_lane(a, i, nb, fl, T, K);
 	} else {
-#pragma unroll
-		for (int k = 0; k < 4; k++)
-			prev[k] = ivw[k];
+		const RkArgs K = { keys.k[0] };
+		cbc_decrypt_lane(a, i, nb, fl, T, K);
 	}
-	for (uint32_t j = 0; j < nb; j++) {
-		const uint32_t bn = j == 0 ? 0u : b + 1;
-		uint32_t cn[4] = { 0, 0, 0, 0 };
-		if (j + 1 < nb)
-			ld16(src + 16 * (uint64_t)bn, cn);
-		uint32_t x[4] = { c[0], c[1], c[2], c[3] };
-		if (ALT)
-			aes_block<true>(T, KL, x);
-		else
-			aes_block<true>(T, KA, x);
-#pragma unroll
-		for (int k = 0; k < 4; k++)
-			x[k] ^= prev[k];
-		if (j == 0) {
-			pad = aes_pkcs7_pad(x);
-			if (pad == 0)
-				break;
-		}
-		st16(dst + 16 * (uint64_t)b, x);
-#pragma unroll
-		for (int k = 0; k < 4; k++) {
-			prev[k] = j == 0 ? ivw[k] : c[k];
-			c[k] = cn[k];
-		}
-		b = bn;
-	}
-	if (pad == 0)
-		a.result[i] = PKT_BAD;
-	a.plen[i] = pad != 0 ? 16 * nb - pad : 0u;
-}
-
-/*
- * TX.  Slot i holds plen[i] plaintext bytes at its payload offset.  With
- * PH_ENCRYPTED they are encrypted in place into 16 * (plen / 16 + 1) bytes
- * (EVP always pads); a slot without the room is RESOURCE and untouched.
- * The next block's plaintext is loaded before the current one goes through
- * the chain; the last, partial block is read bytewise and padded.
- */
-
-/* Slot i's blocks to encrypt; what needs no cipher is settled here. */
-__device__ __forceinline__ uint32_t encrypt_prep(const AesBurstArgs &a,
-    uint64_t i)
-{
-	if (i >= a.n)
-		return 0;
-	const uint32_t fl = a.flags[i];
-	const uint32_t pl = a.plen[i];
-	const uint32_t len = a.lens[i];
-	const uint32_t po = payload_at(fl, a.hashlen);
-	if ((fl & PKT_PH_ENCRYPTED) == 0) {
-		const uint64_t wl = (uint64_t)po + pl;
-		a.wire_len[i] = (uint32_t)wl;
-		a.result[i] = wl > len ? PKT_RESOURCE : PKT_OK;
-		return 0;
-	}
-	const uint64_t clen = 16 * ((uint64_t)pl / 16 + 1);
-	const bool room = po + clen <= len;
-	a.wire_len[i] = room ? po + (uint32_t)clen : 0u;
-	a.result[i] = room ? PKT_OK : PKT_RESOURCE;
-	return room ? (uint32_t)(clen >> 4) : 0u;
 }
 
 __global__ __launch_bounds__(AES_WG) void aes_cbc_encrypt_kernel(
@@ -343,54 +223,13 @@ __global__ __launch_bounds__(AES_WG) void aes_cbc_encrypt_kernel(
 
 	const LdsTab T = { tab + (threadIdx.x & (AES_REP - 1)) };
 	const RkArgs K = { keys.k[0] };
-	uint8_t *p = a.out + a.offsets[i] + payload_at(a.flags[i], a.hashlen);
-	const uint32_t rem = a.plen[i] & 15u;
-	uint32_t chain[4], cur[4];
-
-	/* block j of the padded plaintext: whole, or the tail and its padding */
-	auto load = [&](uint32_t j, uint32_t (&w)[4]) {
-		const uint8_t *q = p + 16 * (uint64_t)j;
-		if (j + 1 < nb) {
-			ld16(q, w);
-			return;
-		}
-		w[0] = w[1] = w[2] = w[3] = 0;
-#pragma unroll
-		for (uint32_t k = 0; k < 16; k++) {
-			const uint32_t v = k < rem ? q[k] : 16u - rem;
-			w[k / 4] |= v << (24 - 8 * (k % 4));
-		}
-	};
-
-	ld16(a.iv + NET2_AES_BLOCK * i, chain);
-	load(0, cur);
-	for (uint32_t j = 0; j < nb; j++) {
-		uint32_t nx[4] = { 0, 0, 0, 0 };
-		if (j + 1 < nb)
-			load(j + 1, nx);
-#pragma unroll
-		for (int k = 0; k < 4; k++)
-			chain[k] ^= cur[k];
-		aes_block<false>(T, K, chain);
-		st16(p + 16 * (uint64_t)j, chain);
-#pragma unroll
-		for (int k = 0; k < 4; k++)
-			cur[k] = nx[k];
-	}
+	cbc_encrypt_lane(a, i, nb, T, K);
 }
 
 /*
- * The same under the keys of each datagram's own connection
- * (net2_packet_{decrypt,encrypt}_burst_mc): datagram i belongs to slot conn[i]
- * of the device cipher-key table (Net2CipherEnt, aes_tab.h).  What needs no
- * cipher work is settled by the datagram's own lane before the ranking, as
- * above; a datagram with cipher work but without a connection -- conn[i] out
- * of range, or the slot's rx (decrypt) / tx (encrypt) side unset -- is
- * PKT_NOCONN there and left untouched: one conn load and one meta load.  An
- * index out of range is clamped to entry 0 before any address is formed from
- * it.  After the ranking lane t looks up the entry of the datagram it owns
- * and takes its schedule from there (RX: the active or the alternate one,
- * picked by address).
+ * The _mc kernels (AesMcArgs and the connection checks: aes_cbc.h).  After
+ * the ranking lane t looks up the entry of the datagram it owns and takes its
+ * schedule from there (RX: ciphertab_rx_key).
  *
  * Round keys: a lane loads the 60 words of its schedule once, as fifteen
  * 16-byte global loads, and holds them in VGPRs for all its blocks (RkRegs;
@@ -402,14 +241,6 @@ __global__ __launch_bounds__(AES_WG) void aes_cbc_encrypt_kernel(
 #ifndef NET2_AES_MC_REREAD
 #define NET2_AES_MC_REREAD 0
 #endif
-constexpr uint8_t PKT_NOCONN = 5;	/* NET2_PBURST_NOCONN */
-
-struct AesMcArgs {
-	AesBurstArgs b;
-	const uint32_t *conn;
-	const Net2CipherEnt *tab;
-	uint32_t slots;
-};
 
 /* Round keys out of a table entry's schedule (16-byte aligned): loaded once
  * into the lane's registers, or read from the table at every use. */
@@ -447,54 +278,6 @@ typedef RkGlobal RkMc;
 typedef RkRegs RkMc;
 #endif
 
-/* The entry of datagram i; *in: its index was in range (else entry 0). */
-__device__ __forceinline__ const Net2CipherEnt *ciphertab_ent(
-    const AesMcArgs &m, uint64_t i, bool *in)
-{
-	const uint32_t c = m.conn[i];
-	*in = c < m.slots;
-	return m.tab + (*in ? c : 0u);
-}
-
-/* Whether datagram i's slot has `side` (NET2_CT_RX / NET2_CT_TX) set. */
-__device__ __forceinline__ bool ciphertab_has(const AesMcArgs &m, uint64_t i,
-    uint32_t side)
-{
-	bool in;
-	const Net2CipherEnt *e = ciphertab_ent(m, i, &in);
-	return in && (e->meta[0] & side) != 0;
-}
-
-/* decrypt_prep, after the connection check of a datagram that would be
- * decrypted (no look-up for any other). */
-__device__ __forceinline__ uint32_t decrypt_mc_prep(const AesMcArgs &m,
-    uint64_t i)
-{
-	const AesBurstArgs &a = m.b;
-	if (i < a.n && a.result[i] == PKT_OK &&
-	    (a.flags[i] & PKT_PH_ENCRYPTED) != 0 && !ciphertab_has(m, i, NET2_CT_RX)) {
-		a.result[i] = PKT_NOCONN;
-		a.plen[i] = 0;
-		return 0;
-	}
-	return decrypt_prep(a, i);
-}
-
-/* encrypt_prep, then the connection check of a slot it found room to encrypt
- * (RESOURCE wins over NOCONN; no look-up for any other). */
-__device__ __forceinline__ uint32_t encrypt_mc_prep(const AesMcArgs &m,
-    uint64_t i)
-{
-	const AesBurstArgs &a = m.b;
-	const uint32_t nb = encrypt_prep(a, i);
-	if (nb != 0 && !ciphertab_has(m, i, NET2_CT_TX)) {
-		a.result[i] = PKT_NOCONN;
-		a.wire_len[i] = 0;
-		return 0;
-	}
-	return nb;
-}
-
 __global__ __launch_bounds__(AES_WG) void aes_cbc_decrypt_mc_kernel(
     const AesMcArgs m)
 {
@@ -511,56 +294,9 @@ __global__ __launch_bounds__(AES_WG) void aes_cbc_decrypt_mc_kernel(
 		return;
 
 	const uint32_t fl = a.flags[i];
-	const uint32_t po = payload_at(fl, a.hashlen);
 	const LdsTab T = { tab + (threadIdx.x & (AES_REP - 1)) };
-	bool in;
-	const Net2CipherEnt *e = ciphertab_ent(m, i, &in);
-	const u32x4 mt = *reinterpret_cast<const u32x4 *>(e->meta);
-	const bool alt = aes_rx_alt((mt.x & NET2_CT_RX_ALT) != 0,
-	    (mt.x & NET2_CT_RX_NOCUT) != 0, fl, a.seq[i], mt.y, mt.z);
-	const RkMc K(e->dec[alt ? 1 : 0]);
-	const uint64_t off = a.offsets[i] + po;
-	const uint8_t *src = a.in + off;
-	uint8_t *dst = a.out + off;
-	uint32_t ivw[4], c[4], prev[4];
-	uint32_t b = nb - 1, pad = 0;
-
-	/* the block order and the loads of aes_cbc_decrypt_kernel */
-	ld16(a.iv + NET2_AES_BLOCK * i, ivw);
-	ld16(src + 16 * (uint64_t)b, c);
-	if (nb > 1) {
-		ld16(src + 16 * (uint64_t)(b - 1), prev);
-	} else {
-#pragma unroll
-		for (int k = 0; k < 4; k++)
-			prev[k] = ivw[k];
-	}
-	for (uint32_t j = 0; j < nb; j++) {
-		const uint32_t bn = j == 0 ? 0u : b + 1;
-		uint32_t cn[4] = { 0, 0, 0, 0 };
-		if (j + 1 < nb)
-			ld16(src + 16 * (uint64_t)bn, cn);
-		uint32_t x[4] = { c[0], c[1], c[2], c[3] };
-		aes_block<true>(T, K, x);
-#pragma unroll
-		for (int k = 0; k < 4; k++)
-			x[k] ^= prev[k];
-		if (j == 0) {
-			pad = aes_pkcs7_pad(x);
-			if (pad == 0)
-				break;
-		}
-		st16(dst + 16 * (uint64_t)b, x);
-#pragma unroll
-		for (int k = 0; k < 4; k++) {
-			prev[k] = j == 0 ? ivw[k] : c[k];
-			c[k] = cn[k];
-		}
-		b = bn;
-	}
-	if (pad == 0)
-		a.result[i] = PKT_BAD;
-	a.plen[i] = pad != 0 ? 16 * nb - pad : 0u;
+	const RkMc K(ciphertab_rx_key(m, i, fl));
+	cbc_decrypt_lane(a, i, nb, fl, T, K);
 }
 
 __global__ __launch_bounds__(AES_WG) void aes_cbc_encrypt_mc_kernel(
@@ -569,7 +305,6 @@ __global__ __launch_bounds__(AES_WG) void aes_cbc_encrypt_mc_kernel(
 	__shared__ uint32_t tab[256 * AES_REP > 2 * AES_WG ? 256 * AES_REP :
 	    2 * AES_WG];
 
-	const AesBurstArgs &a = m.b;
 	const uint64_t first = (uint64_t)blockIdx.x * AES_WG;
 	uint32_t nb;
 	const uint64_t i = first + lanes_by_work(tab,
@@ -581,40 +316,7 @@ __global__ __launch_bounds__(AES_WG) void aes_cbc_encrypt_mc_kernel(
 	const LdsTab T = { tab + (threadIdx.x & (AES_REP - 1)) };
 	bool in;
 	const RkMc K(ciphertab_ent(m, i, &in)->enc);
-	uint8_t *p = a.out + a.offsets[i] + payload_at(a.flags[i], a.hashlen);
-	const uint32_t rem = a.plen[i] & 15u;
-	uint32_t chain[4], cur[4];
-
-	/* block j of the padded plaintext, as in aes_cbc_encrypt_kernel */
-	auto load = [&](uint32_t j, uint32_t (&w)[4]) {
-		const uint8_t *q = p + 16 * (uint64_t)j;
-		if (j + 1 < nb) {
-			ld16(q, w);
-			return;
-		}
-		w[0] = w[1] = w[2] = w[3] = 0;
-#pragma unroll
-		for (uint32_t k = 0; k < 16; k++) {
-			const uint32_t v = k < rem ? q[k] : 16u - rem;
-			w[k / 4] |= v << (24 - 8 * (k % 4));
-		}
-	};
-
-	ld16(a.iv + NET2_AES_BLOCK * i, chain);
-	load(0, cur);
-	for (uint32_t j = 0; j < nb; j++) {
-		uint32_t nx[4] = { 0, 0, 0, 0 };
-		if (j + 1 < nb)
-			load(j + 1, nx);
-#pragma unroll
-		for (int k = 0; k < 4; k++)
-			chain[k] ^= cur[k];
-		aes_block<false>(T, K, chain);
-		st16(p + 16 * (uint64_t)j, chain);
-#pragma unroll
-		for (int k = 0; k < 4; k++)
-			cur[k] = nx[k];
-	}
+	cbc_encrypt_lane(m.b, i, nb, T, K);
 }
 
 /*
@@ -759,12 +461,8 @@ __global__ __launch_bounds__(AES_WG) void aes_cbc_decrypt_wave_kernel(
 
 	const AesBurstArgs &a = w.burst();
 	const uint32_t t = threadIdx.x;
-	if constexpr (KS == KS_ALT) {
-		if (t < NET2_AES_RKWORDS)
-			rks[t] = w.keys.k[0].w[t];
-		else if (t >= 64 && t < 64 + NET2_AES_RKWORDS)
-			rks[AES_RK_STRIDE + t - 64] = w.keys.k[1].w[t - 64];
-	}
+	if constexpr (KS == KS_ALT)
+		stage_rx_keys(rks, w.keys);
 	/* the one barrier (it publishes rks as well): before any wave can end */
 	aes_build_table<true>(tab);
 
@@ -791,18 +489,10 @@ __global__ __launch_bounds__(AES_WG) void aes_cbc_decrypt_wave_kernel(
 			const RkArgs K = { w.keys.k[0] };
 			decrypt_by_wave(a, i, nb, fl, T, K, lane);
 		} else if constexpr (KS == KS_ALT) {
-			/* net2_ck_rx_key, as the HMAC step chose */
-			const bool alt = aes_rx_alt(true, a.no_cutoff != 0, fl, a.seq[i],
-			    a.cutoff, a.rx_start);
-			const RkWave K(rks + (alt ? AES_RK_STRIDE : 0));
+			const RkWave K(staged_rx_key(rks, a, i, fl));
 			decrypt_by_wave(a, i, nb, fl, T, K, lane);
 		} else {
-			bool in;
-			const Net2CipherEnt *e = ciphertab_ent(w.m, i, &in);
-			const u32x4 mt = *reinterpret_cast<const u32x4 *>(e->meta);
-			const bool alt = aes_rx_alt((mt.x & NET2_CT_RX_ALT) != 0,
-			    (mt.x & NET2_CT_RX_NOCUT) != 0, fl, a.seq[i], mt.y, mt.z);
-			const RkWave K(e->dec[alt ? 1 : 0]);
+			const RkWave K(ciphertab_rx_key(w.m, i, fl));
 			decrypt_by_wave(a, i, nb, fl, T, K, lane);
 		}
 	}

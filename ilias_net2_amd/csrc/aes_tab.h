@@ -4,9 +4,11 @@
  * connection's keys.  The _mc cipher kernels (aes_kernels.hip) read entries
  * from global memory; aes_tab_set_kernel there is the only writer.
  *
- * Host code only, plain C++17, no HIP header: aes_kernels.hip includes it, and
- * so does the host check (tests/cxx/test_aes_tab_host.cc).  The functions have
- * internal linkage, as those of aes_sched.h.
+ * Host code only, plain C++17, no HIP header: aes_kernels.hip includes it
+ * (through aes_cbc.h, which has the kernels' look-ups), and so do the host
+ * checks (tests/cxx/test_aes_tab_host.cc).  The functions have internal
+ * linkage, as those of aes_sched.h; inline, so an includer that fills no
+ * entry gets no warning.
  */
 #ifndef NET2_AES_TAB_H
 #define NET2_AES_TAB_H
@@ -43,7 +45,7 @@ namespace {
  * alternate key or NULL, and with one the choice's state (net2_ck_rx_key,
  * src/conn_keys.c:447-476; without one the three are stored as 0).
  */
-void aes_tab_fill_rx(Net2CipherEnt *e, const uint8_t *key,
+inline void aes_tab_fill_rx(Net2CipherEnt *e, const uint8_t *key,
     const uint8_t *alt_key, bool no_cutoff, uint32_t cutoff, uint32_t rx_start)
 {
 	AesSched ks;
@@ -66,7 +68,7 @@ void aes_tab_fill_rx(Net2CipherEnt *e, const uint8_t *key,
 }
 
 /* The tx side of *e: the key the transmitter encrypts with. */
-void aes_tab_fill_tx(Net2CipherEnt *e, const uint8_t *key)
+inline void aes_tab_fill_tx(Net2CipherEnt *e, const uint8_t *key)
 {
 	AesSched ks;
 	aes256_enc_schedule(key, &ks);

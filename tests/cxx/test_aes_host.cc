@@ -4,12 +4,17 @@
  * recovery, the PKCS#7 check) under the schedules of aes_sched.h, with a
  * plain 256-word array as the table and a plain schedule as the round keys,
  * against libcrypto's EVP and against restatements of FIPS 197 written here.
- * No GPU: this is the arithmetic the kernels of aes_kernels.hip run, and the
- * CBC chaining as they do it (RX: last block first; TX: the padded tail).
+ * No GPU: this is the arithmetic the kernels of aes_kernels.hip run.  Then
+ * the lane kernels' own per-datagram code (aes_cbc.h: the prep steps,
+ * cbc_decrypt_lane, cbc_encrypt_lane) over bursts of one datagram in
+ * exact-size heap buffers, bit for bit against EVP and the documented codes:
+ * every block count up to the rotation's third, in place and out of place,
+ * at each payload offset, and what the prep steps settle on their own.
  *
  * Exits non-zero with a message on the first mismatch.
- *   c++ -std=c++17 -Iilias_net2_amd/csrc tests/cxx/test_aes_host.cc -lcrypto
+ *   clang++ -std=c++17 -Iilias_net2_amd/csrc tests/cxx/test_aes_host.cc -lcrypto
  */
+#include "aes_cbc.h"
 #include "aes_device.h"
 #include "aes_sched.h"
 
@@ -20,6 +25,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <initializer_list>
 #include <vector>
 
 namespace {
@@ -376,91 +382,310 @@ void check_pad()
 }
 
 /*
- * RX as aes_cbc_decrypt_kernel chains it: the last block first (its padding
- * decides), then the blocks in order.  Returns the plaintext length, -1 for
- * what the kernel makes BAD.
+ * One datagram through the lane code of aes_cbc.h, as a burst of one: the
+ * datagram sits at the odd offset LEAD of a heap buffer that ends with its
+ * last byte, every per-datagram array is a heap array of one element, so
+ * AddressSanitizer reports any byte touched outside them.  Bytes that must
+ * stay as they are hold a sentinel.
  */
-int cbc_decrypt_as_kernel(const AesSched &d, const uint8_t iv[16],
-    const uint8_t *ct, size_t clen, uint8_t *out)
-{
-	if (clen == 0 || clen % 16 != 0)
-		return -1;
-	const size_t nb = clen / 16;
-	uint8_t x[16];
-	const uint8_t *prev = nb > 1 ? ct + 16 * (nb - 2) : iv;
-	block_dec(d, ct + 16 * (nb - 1), x);
-	uint32_t w[4];
-	for (int k = 0; k < 16; k++)
-		x[k] ^= prev[k];
-	to_words(x, w);
-	const uint32_t pad = aes_pkcs7_pad(w);
-	if (pad == 0)
-		return -1;
-	memcpy(out + 16 * (nb - 1), x, 16);
-	for (size_t b = 0; b + 1 < nb; b++) {
-		prev = b == 0 ? iv : ct + 16 * (b - 1);
-		block_dec(d, ct + 16 * b, x);
-		for (int k = 0; k < 16; k++)
-			out[16 * b + k] = x[k] ^ prev[k];
+constexpr size_t LEAD = 3;
+constexpr uint8_t SENTINEL = 0xc3;
+constexpr uint32_t UNSET = 0xdeadbeefu;
+
+struct One {
+	std::vector<uint64_t> off;
+	std::vector<uint32_t> len, fl, seq, plen, wire;
+	std::vector<uint8_t> iv, res;
+	AesBurstArgs a;
+
+	One(uint32_t length, uint32_t flags, uint32_t hashlen, const uint8_t *ivp,
+	    uint8_t code, uint32_t pl) :
+	    off(1, LEAD), len(1, length), fl(1, flags), seq(1, 0), plen(1, pl),
+	    wire(1, UNSET), iv(ivp, ivp + 16), res(1, code), a()
+	{
+		a.offsets = off.data();
+		a.lens = len.data();
+		a.seq = seq.data();
+		a.flags = fl.data();
+		a.iv = iv.data();
+		a.result = res.data();
+		a.plen = plen.data();
+		a.wire_len = wire.data();
+		a.n = 1;
+		a.hashlen = hashlen;
 	}
-	return (int)(16 * nb - pad);
+};
+
+/* LEAD sentinel bytes, then the datagram */
+std::vector<uint8_t> burst_of(const uint8_t *dg, size_t len)
+{
+	std::vector<uint8_t> b(LEAD + len, SENTINEL);
+	if (len != 0)
+		memcpy(b.data() + LEAD, dg, len);
+	return b;
 }
 
-/* TX as aes_cbc_encrypt_kernel chains it: whole blocks, then the tail and
- * its padding (a whole block of 16 when the length is a multiple of 16). */
-size_t cbc_encrypt_as_kernel(const AesSched &e, const uint8_t iv[16],
-    const uint8_t *pt, size_t plen, uint8_t *out)
+struct Done {
+	uint8_t code;
+	uint32_t plen, wire;
+	uint32_t nb;			/* what the prep step counted */
+	std::vector<uint8_t> bytes;	/* the output burst, LEAD included */
+};
+
+/* RX: decrypt_prep + cbc_decrypt_lane; out of place into a burst of sentinel
+ * bytes, or in place */
+Done rx(const AesSched &d, const uint8_t *iv, uint32_t flags, uint32_t hashlen,
+    const uint8_t *dg, uint32_t len, bool in_place, uint8_t code = PKT_OK)
 {
-	const size_t nb = plen / 16 + 1, rem = plen % 16;
-	uint8_t chain[16], cur[16];
-	memcpy(chain, iv, 16);
-	for (size_t j = 0; j < nb; j++) {
-		for (size_t k = 0; k < 16; k++)
-			cur[k] = j + 1 < nb ? pt[16 * j + k] :
-			    k < rem ? pt[16 * j + k] : (uint8_t)(16 - rem);
-		for (int k = 0; k < 16; k++)
-			chain[k] ^= cur[k];
-		block_enc(e, chain, chain);
-		memcpy(out + 16 * j, chain, 16);
-	}
-	return 16 * nb;
+	One o(len, flags, hashlen, iv, code, UNSET);
+	std::vector<uint8_t> in = burst_of(dg, len);
+	std::vector<uint8_t> out(in_place ? 0 : LEAD + len, SENTINEL);
+	o.a.in = in.data();
+	o.a.out = in_place ? in.data() : out.data();
+	const uint32_t nb = decrypt_prep(o.a, 0);
+	if (nb != 0)
+		cbc_decrypt_lane(o.a, 0, nb, flags, Tab{ Td0 }, Rk{ d.w });
+	if (o.wire[0] != UNSET)
+		fail("RX wrote wire_len");
+	return Done{ o.res[0], o.plen[0], 0, nb, in_place ? in : out };
 }
 
+/* TX: encrypt_prep + cbc_encrypt_lane over the slot, in place */
+Done tx(const AesSched &e, const uint8_t *iv, uint32_t flags, uint32_t hashlen,
+    const uint8_t *slot, uint32_t len, uint32_t plen)
+{
+	One o(len, flags, hashlen, iv, 9, plen);
+	std::vector<uint8_t> b = burst_of(slot, len);
+	o.a.out = b.data();
+	const uint32_t nb = encrypt_prep(o.a, 0);
+	if (nb != 0)
+		cbc_encrypt_lane(o.a, 0, nb, Tab{ Te0 }, Rk{ e.w });
+	if (o.plen[0] != plen)
+		fail("TX wrote plen");
+	return Done{ o.res[0], plen, o.wire[0], nb, b };
+}
+
+bool all_are(const uint8_t *p, size_t n, uint8_t v)
+{
+	for (size_t i = 0; i < n; i++)
+		if (p[i] != v)
+			return false;
+	return true;
+}
+
+/* where the payload lies: PH_ENCRYPTED alone, and PH_SIGNED under each hash */
+struct Layout {
+	uint32_t flags, hashlen, po;
+};
+const Layout layouts[] = {
+	{ PKT_PH_ENCRYPTED, 0, 8 },
+	{ PKT_PH_ENCRYPTED, 64, 8 },	/* hashlen counts only with PH_SIGNED */
+	{ PKT_PH_ENCRYPTED | PKT_PH_SIGNED, 32, 40 },
+	{ PKT_PH_ENCRYPTED | PKT_PH_SIGNED, 48, 56 },
+	{ PKT_PH_ENCRYPTED | PKT_PH_SIGNED, 64, 72 },
+};
+
+/* Both directions, bit for bit against EVP: every length, every layout. */
 void check_cbc()
 {
-	const size_t lens[] = { 0, 1, 15, 16, 17, 31, 32, 33, 1472 };
+	/* 1, 2, 3, 4, 92 and 93 blocks of ciphertext among them */
+	const size_t lens[] = { 0, 1, 15, 16, 17, 31, 32, 33, 47, 48, 63, 1456, 1471,
+	    1472 };
+	bool blocks[94] = {};
+	unsigned refused = 0, refused_long = 0;
 	uint8_t key[32], iv[16];
-	std::vector<uint8_t> pt(1472), ct(1472 + 32), want(1472 + 32), back(1472 + 32);
-	for (size_t len : lens) {
-		rnd_bytes(key, 32);
-		rnd_bytes(iv, 16);
-		rnd_bytes(pt.data(), len);
-		AesSched e, d;
-		aes256_enc_schedule(key, &e);
-		aes256_dec_schedule(key, &d);
-		const int wn = evp_run(EVP_aes_256_cbc(), true, key, iv, true, pt.data(),
-		    len, want.data());
-		const size_t n = cbc_encrypt_as_kernel(e, iv, pt.data(), len, ct.data());
-		if (wn != (int)n || memcmp(ct.data(), want.data(), n) != 0)
-			fail("CBC encrypt, %zu bytes: %zu bytes %s..., EVP %d bytes %s...",
-			    len, n, hex(ct.data(), 16), wn, hex(want.data(), 16));
-		const int pn = cbc_decrypt_as_kernel(d, iv, want.data(), n, back.data());
-		if (pn != (int)len || memcmp(back.data(), pt.data(), len) != 0)
-			fail("CBC decrypt, %zu bytes: got %d bytes", len, pn);
-		/* EVP agrees that this is what the ciphertext holds */
-		const int en = evp_run(EVP_aes_256_cbc(), false, key, iv, true,
-		    want.data(), n, back.data());
-		if (en != (int)len || memcmp(back.data(), pt.data(), len) != 0)
-			fail("EVP CBC decrypt, %zu bytes: %d", len, en);
-		/* a last block whose padding is wrong: both refuse */
-		want[n - 1] ^= 0x80;
-		const int bad_k = cbc_decrypt_as_kernel(d, iv, want.data(), n, back.data());
-		const int bad_e = evp_run(EVP_aes_256_cbc(), false, key, iv, true,
-		    want.data(), n, back.data());
-		if ((bad_k < 0) != (bad_e < 0) || (bad_k >= 0 && bad_k != bad_e))
-			fail("CBC decrypt of a damaged last block, %zu bytes: %d, EVP %d",
-			    len, bad_k, bad_e);
+	std::vector<uint8_t> pt(1472), want(1472 + 32), back(1472 + 32);
+	for (size_t len : lens)
+		for (const Layout &l : layouts) {
+			rnd_bytes(key, 32);
+			rnd_bytes(iv, 16);
+			rnd_bytes(pt.data(), len);
+			AesSched e, d;
+			aes256_enc_schedule(key, &e);
+			aes256_dec_schedule(key, &d);
+			const int wn = evp_run(EVP_aes_256_cbc(), true, key, iv, true, pt.data(),
+			    len, want.data());
+			if (wn != (int)(16 * (len / 16 + 1)))
+				fail("EVP CBC encrypt, %zu bytes: %d", len, wn);
+			const uint32_t n = (uint32_t)wn, po = l.po;
+			if (payload_at(l.flags, l.hashlen) != po)
+				fail("payload_at(%x, %u) = %u", l.flags, l.hashlen,
+				    payload_at(l.flags, l.hashlen));
+			blocks[n / 16] = true;
+
+			/* TX: a slot of exactly header + ciphertext, the plaintext in it */
+			std::vector<uint8_t> slot(po + n, 0x5a);
+			rnd_bytes(slot.data(), po);
+			memcpy(slot.data() + po, pt.data(), len);
+			const Done t = tx(e, iv, l.flags, l.hashlen, slot.data(), po + n,
+			    (uint32_t)len);
+			if (t.code != PKT_OK || t.wire != po + n || t.nb != n / 16)
+				fail("CBC encrypt, %zu bytes at %u: code %u, wire_len %u, %u blocks",
+				    len, po, t.code, t.wire, t.nb);
+			if (memcmp(&t.bytes[LEAD + po], want.data(), n) != 0)
+				fail("CBC encrypt, %zu bytes at %u: %s..., EVP %s...", len, po,
+				    hex(&t.bytes[LEAD + po], 16), hex(want.data(), 16));
+			if (!all_are(t.bytes.data(), LEAD, SENTINEL) ||
+			    memcmp(&t.bytes[LEAD], slot.data(), po) != 0)
+				fail("CBC encrypt, %zu bytes at %u: wrote before the payload", len, po);
+
+			/* RX of that datagram, out of place and in place */
+			const uint8_t *dg = &t.bytes[LEAD];
+			const Done r = rx(d, iv, l.flags, l.hashlen, dg, po + n, false);
+			if (r.code != PKT_OK || r.plen != len || r.nb != n / 16)
+				fail("CBC decrypt, %zu bytes at %u: code %u, plen %u, %u blocks", len,
+				    po, r.code, r.plen, r.nb);
+			if (memcmp(&r.bytes[LEAD + po], pt.data(), len) != 0)
+				fail("CBC decrypt, %zu bytes at %u: wrong plaintext", len, po);
+			if (!all_are(r.bytes.data(), LEAD + po, SENTINEL))
+				fail("CBC decrypt, %zu bytes at %u: wrote before the payload", len, po);
+			const Done ri = rx(d, iv, l.flags, l.hashlen, dg, po + n, true);
+			if (ri.code != PKT_OK || ri.plen != len ||
+			    memcmp(&ri.bytes[LEAD + po], &r.bytes[LEAD + po], n) != 0)
+				fail("CBC decrypt in place, %zu bytes at %u: code %u, plen %u, or "
+				    "other bytes than out of place", len, po, ri.code, ri.plen);
+			if (!all_are(ri.bytes.data(), LEAD, SENTINEL) ||
+			    memcmp(&ri.bytes[LEAD], dg, po) != 0)
+				fail("CBC decrypt in place, %zu bytes at %u: wrote before the "
+				    "payload", len, po);
+			/* EVP agrees that this is what the ciphertext holds */
+			const int en = evp_run(EVP_aes_256_cbc(), false, key, iv, true,
+			    want.data(), n, back.data());
+			if (en != (int)len || memcmp(back.data(), pt.data(), len) != 0)
+				fail("EVP CBC decrypt, %zu bytes: %d", len, en);
+
+			/* a last block whose padding is wrong: both refuse, and a refused
+			 * datagram is BAD, plen 0, not a byte of it written */
+			std::vector<uint8_t> bad(dg, dg + po + n);
+			bad[po + n - 1] ^= 0x80;
+			const int bad_e = evp_run(EVP_aes_256_cbc(), false, key, iv, true,
+			    &bad[po], n, back.data());
+			for (int in_place = 0; in_place < 2; in_place++) {
+				const Done b = rx(d, iv, l.flags, l.hashlen, bad.data(), po + n,
+				    in_place != 0);
+				if ((b.code == PKT_BAD) != (bad_e < 0) ||
+				    (b.code != PKT_BAD && (b.code != PKT_OK || (int)b.plen != bad_e)))
+					fail("CBC decrypt of a damaged last block, %zu bytes: code "
+					    "%u, plen %u, EVP %d", len, b.code, b.plen, bad_e);
+				if (b.code != PKT_BAD)
+					continue;
+				refused++;
+				refused_long += n / 16 >= 3;
+				if (b.plen != 0)
+					fail("a BAD datagram's plen is %u", b.plen);
+				if (in_place ? memcmp(&b.bytes[LEAD], bad.data(), po + n) != 0 :
+				    !all_are(b.bytes.data(), LEAD + po + n, SENTINEL))
+					fail("a BAD datagram of %zu bytes at %u was written", len, po);
+			}
+		}
+	for (int nb : { 1, 2, 3, 4, 92, 93 })
+		if (!blocks[nb])
+			fail("no case of %d blocks", nb);
+	if (refused == 0 || refused_long == 0)
+		fail("no damaged datagram was refused (%u, %u of three blocks and more)",
+		    refused, refused_long);
+}
+
+/* What RX settles without the cipher (decrypt_prep). */
+void check_rx_prep()
+{
+	uint8_t key[32], iv[16];
+	rnd_bytes(key, 32);
+	rnd_bytes(iv, 16);
+	AesSched d;
+	aes256_dec_schedule(key, &d);
+	std::vector<uint8_t> dg(72 + 64);
+	rnd_bytes(dg.data(), dg.size());
+
+	auto untouched = [](const Done &r, const char *what, uint32_t len) {
+		if (r.nb != 0 || r.plen != 0 ||
+		    !all_are(r.bytes.data(), r.bytes.size(), SENTINEL))
+			fail("%s, %u bytes: %u blocks, plen %u, or bytes written", what, len,
+			    r.nb, r.plen);
+	};
+	for (const Layout &l : layouts) {
+		/* empty and ragged ciphertext; a datagram that ends at or before
+		 * its payload */
+		for (uint32_t len : { l.po + 0, l.po + 15, l.po + 17, l.po + 1, l.po + 31,
+		    l.po - 1, 1u, 0u }) {
+			const Done r = rx(d, iv, l.flags, l.hashlen, dg.data(), len, false);
+			if (r.code != PKT_BAD)
+				fail("RX prep, %u bytes at %u: code %u, want BAD", len, l.po, r.code);
+			untouched(r, "RX prep", len);
+		}
+		/* no PH_ENCRYPTED, or not OK on arrival: the code stays */
+		const uint32_t len = l.po + 64;
+		const Done c = rx(d, iv, l.flags & ~PKT_PH_ENCRYPTED, l.hashlen, dg.data(),
+		    len, false);
+		if (c.code != PKT_OK)
+			fail("RX prep, a clear datagram: code %u", c.code);
+		untouched(c, "RX prep, clear", len);
+		for (uint8_t code : { PKT_RESOURCE, PKT_BAD, (uint8_t)3, PKT_NOCONN,
+		    (uint8_t)255 }) {
+			const Done r = rx(d, iv, l.flags, l.hashlen, dg.data(), len, false, code);
+			if (r.code != code)
+				fail("RX prep, arriving with code %u: code %u", code, r.code);
+			untouched(r, "RX prep, not OK", len);
+		}
 	}
+	/* i >= n: nothing read, nothing written (n = 1: the arrays end after
+	 * element 0; n = 0: there are none) */
+	One o(72 + 64, 3, 64, iv, PKT_OK, UNSET);
+	AesBurstArgs none = {};
+	if (decrypt_prep(o.a, 1) != 0 || decrypt_prep(o.a, ~(uint64_t)0) != 0 ||
+	    decrypt_prep(none, 0) != 0 || o.res[0] != PKT_OK || o.plen[0] != UNSET)
+		fail("RX prep past the burst's end");
+}
+
+/* What TX settles without the cipher (encrypt_prep). */
+void check_tx_prep()
+{
+	uint8_t key[32], iv[16];
+	rnd_bytes(key, 32);
+	rnd_bytes(iv, 16);
+	AesSched e;
+	aes256_enc_schedule(key, &e);
+	std::vector<uint8_t> slot(72 + 112);
+	rnd_bytes(slot.data(), slot.size());
+
+	auto untouched = [&](const Done &t, const char *what) {
+		if (t.nb != 0 || !all_are(t.bytes.data(), LEAD, SENTINEL) ||
+		    memcmp(&t.bytes[LEAD], slot.data(), t.bytes.size() - LEAD) != 0)
+			fail("%s: %u blocks, or bytes written", what, t.nb);
+	};
+	for (const Layout &l : layouts)
+		for (uint32_t plen : { 0u, 1u, 15u, 16u, 17u, 95u, 96u }) {
+			const uint32_t po = l.po, fit = po + 16 * (plen / 16 + 1);
+			/* one byte short of the room: RESOURCE; an exact fit: OK */
+			const Done s = tx(e, iv, l.flags, l.hashlen, slot.data(), fit - 1, plen);
+			if (s.code != PKT_RESOURCE || s.wire != 0)
+				fail("TX prep, %u bytes in a slot of %u: code %u, wire_len %u",
+				    plen, fit - 1, s.code, s.wire);
+			untouched(s, "TX prep, a slot one byte short");
+			const Done f = tx(e, iv, l.flags, l.hashlen, slot.data(), fit, plen);
+			if (f.code != PKT_OK || f.wire != fit || f.nb != plen / 16 + 1)
+				fail("TX prep, %u bytes in a slot of %u: code %u, wire_len %u",
+				    plen, fit, f.code, f.wire);
+			/* no PH_ENCRYPTED: the length as it is, RESOURCE past the slot */
+			const uint32_t clear = l.flags & ~PKT_PH_ENCRYPTED;
+			const Done c = tx(e, iv, clear, l.hashlen, slot.data(), po + plen, plen);
+			if (c.code != PKT_OK || c.wire != po + plen)
+				fail("TX prep, clear, %u bytes: code %u, wire_len %u", plen, c.code,
+				    c.wire);
+			untouched(c, "TX prep, a clear slot");
+			if (plen == 0)
+				continue;
+			const Done p = tx(e, iv, clear, l.hashlen, slot.data(), po + plen - 1, plen);
+			if (p.code != PKT_RESOURCE || p.wire != po + plen)
+				fail("TX prep, clear, %u bytes past the slot: code %u, wire_len %u",
+				    plen, p.code, p.wire);
+			untouched(p, "TX prep, a clear slot too short");
+		}
+	One o(72 + 64, 3, 64, iv, 9, 17);
+	AesBurstArgs none = {};
+	if (encrypt_prep(o.a, 1) != 0 || encrypt_prep(o.a, ~(uint64_t)0) != 0 ||
+	    encrypt_prep(none, 0) != 0 || o.res[0] != 9 || o.wire[0] != UNSET)
+		fail("TX prep past the burst's end");
 }
 
 }	/* namespace */
@@ -473,6 +698,8 @@ int main()
 	check_block_cipher();
 	check_pad();
 	check_cbc();
+	check_rx_prep();
+	check_tx_prep();
 	printf("test_aes_host: ok\n");
 	return 0;
 }

@@ -8,11 +8,16 @@
  *   - aes_rx_alt against a plain restatement of net2_ck_rx_key
  *     (src/conn_keys.c:447-476) over a grid that wraps around 2^32;
  *   - an entry's schedules run the SP 800-38A F.2.5 / F.2.6 chain through
- *     aes_block.
+ *     aes_block;
+ *   - the _mc kernels' own connection checks and key pick (aes_cbc.h:
+ *     decrypt_mc_prep, encrypt_mc_prep, ciphertab_rx_key) over an exact-size
+ *     table of two entries: NOCONN for a slot out of range or with the side
+ *     unset, RESOURCE before NOCONN, no look-up where no cipher is needed.
  *
  * Exits non-zero with a message on the first mismatch.
- *   c++ -std=c++17 -Iilias_net2_amd/csrc tests/cxx/test_aes_tab_host.cc
+ *   clang++ -std=c++17 -Iilias_net2_amd/csrc tests/cxx/test_aes_tab_host.cc
  */
+#include "aes_cbc.h"
 #include "aes_device.h"
 #include "aes_sched.h"
 #include "aes_tab.h"
@@ -24,6 +29,7 @@
 #include <string.h>
 
 #include <initializer_list>
+#include <vector>
 
 namespace {
 
@@ -272,6 +278,131 @@ void check_chain()
 	}
 }
 
+/*
+ * The _mc lane and wave kernels' connection checks and key pick (aes_cbc.h)
+ * over a burst of one datagram and a table of exactly two entries on the
+ * heap, every per-datagram array a heap array of one element: what lies
+ * outside them AddressSanitizer reports.
+ */
+constexpr uint32_t UNSET = 0xdeadbeefu;
+
+struct One {
+	std::vector<uint64_t> off;
+	std::vector<uint32_t> len, fl, seq, plen, wire, conn;
+	std::vector<uint8_t> res;
+	AesMcArgs m;
+
+	One(const std::vector<Net2CipherEnt> *tab, uint32_t c, uint32_t length,
+	    uint32_t flags, uint8_t code, uint32_t pl) :
+	    off(1, 0), len(1, length), fl(1, flags), seq(1, 0), plen(1, pl),
+	    wire(1, UNSET), conn(1, c), res(1, code), m()
+	{
+		m.b.offsets = off.data();
+		m.b.lens = len.data();
+		m.b.seq = seq.data();
+		m.b.flags = fl.data();
+		m.b.result = res.data();
+		m.b.plen = plen.data();
+		m.b.wire_len = wire.data();
+		m.b.n = 1;
+		m.b.hashlen = 64;
+		m.conn = conn.data();
+		m.tab = tab != nullptr ? tab->data() : nullptr;
+		m.slots = tab != nullptr ? (uint32_t)tab->size() : 0;
+	}
+};
+
+void check_mc_prep()
+{
+	uint8_t k0[32], k1[32];
+	key_of(0, k0);
+	key_of(1, k1);
+	/* a: entry 0 with both sides and an alternate rx key, entry 1 rx alone;
+	 * b: entry 0 tx alone, entry 1 unset */
+	std::vector<Net2CipherEnt> a(2), b(2);
+	aes_tab_fill_rx(&a[0], k0, k1, false, 100, 50);
+	aes_tab_fill_tx(&a[0], k0);
+	aes_tab_fill_rx(&a[1], k1, nullptr, false, 0, 0);
+	aes_tab_fill_tx(&b[0], k0);
+	const uint32_t ES = PKT_PH_ENCRYPTED | PKT_PH_SIGNED, po = 72;
+
+	struct Case {
+		const std::vector<Net2CipherEnt> *tab;
+		uint32_t conn;
+		bool rx, tx;	/* the datagram has a connection to decrypt / encrypt */
+	};
+	const Case cases[] = {
+		{ &a, 0, true, true }, { &a, 1, true, false }, { &b, 0, false, true },
+		{ &b, 1, false, false },
+		/* out of range: clamped, nothing read past the table */
+		{ &a, 2, false, false }, { &a, 3, false, false },
+		{ &a, 0x80000000u, false, false }, { &a, 0xffffffffu, false, false },
+	};
+	for (const Case &c : cases) {
+		/* RX: four blocks of ciphertext */
+		One r(c.tab, c.conn, po + 64, ES, PKT_OK, UNSET);
+		const uint32_t nb = decrypt_mc_prep(r.m, 0);
+		if (c.rx ? (nb != 4 || r.res[0] != PKT_OK || r.plen[0] != UNSET) :
+		    (nb != 0 || r.res[0] != PKT_NOCONN || r.plen[0] != 0))
+			fail("RX _mc prep, slot %u: %u blocks, code %u, plen %u", c.conn, nb,
+			    r.res[0], r.plen[0]);
+		/* TX: 17 bytes into an exact fit of two blocks */
+		One t(c.tab, c.conn, po + 32, ES, 9, 17);
+		const uint32_t tb = encrypt_mc_prep(t.m, 0);
+		if (c.tx ? (tb != 2 || t.res[0] != PKT_OK || t.wire[0] != po + 32) :
+		    (tb != 0 || t.res[0] != PKT_NOCONN || t.wire[0] != 0))
+			fail("TX _mc prep, slot %u: %u blocks, code %u, wire_len %u", c.conn,
+			    tb, t.res[0], t.wire[0]);
+		/* TX one byte short: RESOURCE, whatever the connection */
+		One s(c.tab, c.conn, po + 31, ES, 9, 17);
+		if (encrypt_mc_prep(s.m, 0) != 0 || s.res[0] != PKT_RESOURCE ||
+		    s.wire[0] != 0)
+			fail("TX _mc prep, slot %u, no room: code %u, wire_len %u", c.conn,
+			    s.res[0], s.wire[0]);
+	}
+	/* what needs no cipher does no look-up: no table, a slot out of range */
+	for (uint32_t conn : { 0u, 7u, 0xffffffffu }) {
+		One clear(nullptr, conn, po + 64, PKT_PH_SIGNED, PKT_OK, UNSET);
+		if (decrypt_mc_prep(clear.m, 0) != 0 || clear.res[0] != PKT_OK ||
+		    clear.plen[0] != 0)
+			fail("RX _mc prep, a clear datagram: code %u", clear.res[0]);
+		One late(nullptr, conn, po + 64, ES, PKT_BAD, UNSET);
+		if (decrypt_mc_prep(late.m, 0) != 0 || late.res[0] != PKT_BAD ||
+		    late.plen[0] != 0)
+			fail("RX _mc prep, arriving BAD: code %u", late.res[0]);
+		One tclear(nullptr, conn, po + 17, PKT_PH_SIGNED, 9, 17);
+		if (encrypt_mc_prep(tclear.m, 0) != 0 || tclear.res[0] != PKT_OK ||
+		    tclear.wire[0] != po + 17)
+			fail("TX _mc prep, a clear slot: code %u, wire_len %u", tclear.res[0],
+			    tclear.wire[0]);
+		One tshort(nullptr, conn, po + 31, ES, 9, 17);
+		if (encrypt_mc_prep(tshort.m, 0) != 0 || tshort.res[0] != PKT_RESOURCE)
+			fail("TX _mc prep, no room and no table: code %u", tshort.res[0]);
+		One past(nullptr, conn, po + 64, ES, PKT_OK, UNSET);
+		if (decrypt_mc_prep(past.m, 1) != 0 || encrypt_mc_prep(past.m, 1) != 0 ||
+		    past.res[0] != PKT_OK || past.plen[0] != UNSET || past.wire[0] != UNSET)
+			fail("_mc prep past the burst's end");
+	}
+
+	/* the key pick: the alternate schedule exactly when aes_rx_alt says so */
+	unsigned picks[2] = { 0, 0 };
+	for (uint32_t slot = 0; slot < 2; slot++)
+		for (uint32_t fl : { ES, ES | 0x80000000u })
+			for (uint32_t seq : { 0u, 49u, 50u, 99u, 100u, 101u, 0xffffffffu }) {
+				One r(&a, slot, po + 64, fl, PKT_OK, UNSET);
+				r.seq[0] = seq;
+				const bool alt = aes_rx_alt(slot == 0, false, fl, seq, 100, 50);
+				if (slot == 1 && alt)
+					fail("aes_rx_alt without an alternate key");
+				if (ciphertab_rx_key(r.m, 0, fl) != a[slot].dec[alt ? 1 : 0])
+					fail("ciphertab_rx_key, slot %u, flags %08x, seq %u: not "
+					    "schedule %d", slot, fl, seq, alt ? 1 : 0);
+				picks[alt ? 1 : 0]++;
+			}
+	if (picks[0] == 0 || picks[1] == 0)
+		fail("key pick: %u active, %u alternate", picks[0], picks[1]);
+}
+
 }	/* namespace */
 
 int main()
@@ -280,6 +411,7 @@ int main()
 	check_fill();
 	check_rx_choice();
 	check_chain();
+	check_mc_prep();
 	printf("test_aes_tab_host: ok\n");
 	return 0;
 }

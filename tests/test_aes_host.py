@@ -4,7 +4,10 @@ tests/cxx/test_aes_host.cc includes aes_device.h (the T-table rounds, the
 last round's S-box recovery, the PKCS#7 check) and aes_sched.h (the key
 schedules the launches make) with plain arrays plugged in, and holds them to
 FIPS 197 and to libcrypto's EVP: the arithmetic of the kernels in
-aes_kernels.hip, run without a GPU.  Built here under AddressSanitizer and
+aes_kernels.hip, run without a GPU.  It then runs the lane kernels' own
+per-datagram code (aes_cbc.h: the prep steps and the CBC chain of each
+direction) over one-datagram bursts in exact-size heap buffers, bit for bit
+against EVP and the documented codes.  Built here under AddressSanitizer and
 UBSan as a stand-alone program and run as a child process; it exits non-zero
 with a message on the first mismatch.
 """

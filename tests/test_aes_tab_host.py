@@ -3,8 +3,10 @@ on the host.
 
 tests/cxx/test_aes_tab_host.cc includes aes_tab.h (the entry of
 ``struct net2_burst_ciphertab`` and how it is filled from keys), aes_sched.h
-and aes_device.h (aes_rx_alt, aes_block) with plain arrays plugged in: what the
-_mc cipher kernels of aes_kernels.hip read and decide, run without a GPU.
+and aes_device.h (aes_rx_alt, aes_block) with plain arrays plugged in, and
+aes_cbc.h (the _mc kernels' connection checks and key pick) over an exact-size
+table: what the _mc cipher kernels of aes_kernels.hip read and decide, run
+without a GPU.
 Built here under AddressSanitizer and UBSan as a stand-alone program and run
 as a child process; it exits non-zero with a message on the first mismatch.
 """

@@ -45,6 +45,26 @@ def dev():
     return torch.device("cuda:0")
 
 
+@pytest.fixture(autouse=True)
+def lane_form():
+    """Every decrypt burst of this module's tests -- and of
+    test_gpu_aes_burst_mc.py's, which imports this fixture -- in the lane
+    form: at the default limit all but the largest would take the wave form,
+    which test_gpu_aes_burst_wave.py runs them in (it calls the test
+    functions as plain functions, so this fixture does not reach it).  Every
+    decrypt launch counts in exactly one of net2_aes_burst_stats' two
+    counters: none in the wave form means each took the lane form."""
+    from ilias_net2_amd import cipher_burst
+    cipher_burst.limits(0)
+    before = cipher_burst.stats()
+    try:
+        yield
+        after = cipher_burst.stats()
+    finally:
+        cipher_burst.limits(-1)
+    assert after["wave_launches"] == before["wave_launches"]
+
+
 def _dev(a, dev):
     return torch.from_numpy(np.array(a, order="C")).to(dev)
 

@@ -20,6 +20,7 @@ import pytest
 
 import aes_ref
 import test_gpu_packet as P
+from test_gpu_aes_burst import lane_form  # noqa: F401  (autouse: the lane form)
 
 pytestmark = pytest.mark.gpu
 
