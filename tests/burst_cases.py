@@ -45,6 +45,10 @@ BLOCK = {4: 64, 5: 128, 6: 128}
 WAVE = 64
 WANT = PH_SIGNED | PH_ENCRYPTED     # the flags the keys call for (cipher set)
 IVLEN = 16
+# IV lengths on both sides of one hash round (<= 32) against two, whole
+# 16-byte pieces against not, rows alternating between 0 and 8 (mod 16) in an
+# aligned array (24), and both ends of the range the C ABI accepts
+IVLENS = (0, 1, 8, 15, 16, 17, 24, 31, 32, 33, 47, 48, 63, 64)
 A16, A4, A1 = "A16", "A4", "A1"
 ALGS = (4, 5, 6)
 

@@ -4,7 +4,8 @@ address mode of every wave), and the oracle alone -- encode, the case's
 edits, decode -- produces exactly the codes the case states, so what
 tests/test_gpu_burst_lattice.py demands of the kernels is what the reference
 does with these inputs.  The oracle's HMAC at every lattice length is held
-against Python's hmac / hashlib.
+against Python's hmac / hashlib, and so are its IV rows at every IV length
+the GPU tests use.
 """
 import hashlib
 import hmac as pyhmac
@@ -170,6 +171,47 @@ def test_L4_uniform_only_after_binning(oracle_mod, alg):
     assert set(e.plen[e.cls == 2]) == {2 * B.BLOCK[alg]}
     a = oracle_codes(oracle_mod, c)
     assert (a.rx_res == B.OK).all()
+
+
+def hashlib_iv(seq, flags, ivlen):
+    """net2_ph_to_iv restated: the first ivlen bytes of D0 || D1, D0 =
+    SHA-256(ph), D1 = SHA-256(ph || D0), ph = be32(seq) || be32(flags)."""
+    out = np.zeros((len(seq), ivlen), dtype=np.uint8)
+    for i, (s, f) in enumerate(zip(seq, flags)):
+        ph = int(s).to_bytes(4, "big") + int(f).to_bytes(4, "big")
+        d0 = hashlib.sha256(ph).digest()
+        iv = (d0 + hashlib.sha256(ph + d0).digest())[:ivlen]
+        out[i] = np.frombuffer(iv, dtype=np.uint8)
+    return out
+
+
+@pytest.mark.parametrize("ivlen", B.IVLENS)
+def test_iv_reference_at_every_length(oracle_mod, ivlen):
+    """The IV rows that the GPU tests expect at every length of B.IVLENS:
+    packet_decode_batch's rows of the OK datagrams are ph_to_iv_batch's, on
+    the every-bit case and on 500 random headers, and both are the first
+    ivlen bytes of the two SHA-256 rounds as hashlib computes them -- so no
+    length rests on the oracle's own loop alone."""
+    c = B.B1(6, 8, 100)
+    a = B.answers(oracle_mod, c)
+    res, iv, seq, fl = oracle_mod.packet_decode_batch(
+        6, a.keys[0], True, ivlen, a.rx, c.offs, c.expect.rx_lens, nthreads=1)
+    assert np.array_equal(res, a.rx_res) and iv.shape == (c.expect.n, ivlen)
+    assert np.array_equal(seq, a.rx_seq) and np.array_equal(fl, a.rx_fl)
+    ok = res == B.OK
+    assert 64 <= ok.sum() < c.expect.n
+    rows = oracle_mod.ph_to_iv_batch(seq, fl, ivlen, nthreads=1)
+    assert np.array_equal(iv[ok], rows[ok])
+    assert not iv[~ok].any()
+    assert np.array_equal(rows, hashlib_iv(seq, fl, ivlen))
+    if ivlen == B.IVLEN:
+        assert np.array_equal(iv, a.rx_iv)
+    rng = np.random.default_rng(616)
+    seq = rng.integers(0, 2**32, 500, dtype=np.uint64).astype(np.uint32)
+    fl = rng.integers(0, 2**32, 500, dtype=np.uint64).astype(np.uint32)
+    rows = oracle_mod.ph_to_iv_batch(seq, fl, ivlen, nthreads=1)
+    assert rows.shape == (500, ivlen)
+    assert np.array_equal(rows, hashlib_iv(seq, fl, ivlen))
 
 
 @pytest.mark.parametrize("plen", [100, 0])

@@ -65,6 +65,24 @@ def lane_form():
     assert after["wave_launches"] == before["wave_launches"]
 
 
+# net2_sha2_burst_limits' arguments for each form of the keyed hash bursts
+# (tests/test_gpu_burst_lattice.py): hmac_kernel in submission order, the same
+# in the length-binned order, burst_wave_kernel
+HASH_FORMS = {"lane": (0, -1), "binned": (0, 1), "wave": (1 << 30, -1)}
+
+
+@pytest.fixture
+def hash_form():
+    """net2_sha2_burst_limits for one test, the defaults restored after."""
+    from ilias_net2_amd import _lib
+    L = _lib.lib()
+
+    def set_form(form):
+        assert L.net2_sha2_burst_limits(*HASH_FORMS[form]) == 0
+    yield set_form
+    L.net2_sha2_burst_limits(-1, -1)
+
+
 def _dev(a, dev):
     return torch.from_numpy(np.array(a, order="C")).to(dev)
 
@@ -390,8 +408,22 @@ def test_chain_on_one_stream_no_cutoff(dev, oracle_mod):
 
 
 def _chain_on_one_stream(dev, oracle_mod, no_cutoff):
-    from ilias_net2_amd import _lib, cipher_burst
-    L = _lib.lib()
+    c = chain_case(no_cutoff)
+    t = chain_device(dev, c)
+    s = torch.cuda.Stream(device=dev)
+    torch.cuda.synchronize()                        # inputs are in place
+    with torch.cuda.stream(s):
+        o = chain_body(dev, c, t, s)
+    s.synchronize()
+    chain_check(oracle_mod, c, o)
+
+
+@functools.lru_cache(maxsize=None)
+def chain_case(no_cutoff, fresh=False):
+    """The chain's burst on the host: n = 200 under row 6 with an alternate
+    key installed, a tenth of the datagrams tampered with after sealing.
+    fresh: the same geometry, keys and headers over other plaintext bytes.
+    Built once; the tests leave it unchanged."""
     rng = np.random.default_rng(4400)
     n, hash_alg, hl = 200, 6, 64
     hkey, halt = (rng.integers(0, 256, hl, dtype=np.uint8).tobytes() for _ in range(2))
@@ -411,66 +443,98 @@ def _chain_on_one_stream(dev, oracle_mod, no_cutoff):
     lens = (po + 16 * (plen // 16 + 1)).astype(np.uint32)
     offs, total = _place(lens, rng)
     data = rng.integers(0, 256, total, dtype=np.uint8)
-    plains = [data[int(offs[i]) + po:int(offs[i]) + po + int(plen[i])].tobytes()
-              for i in range(n)]
     flip = np.nonzero(rng.random(n) < 0.1)[0]       # tampered after sealing
     flip_at = np.array([int(offs[i]) + po + int(rng.integers(0, lens[i] - po))
                         for i in flip], dtype=np.int64)
+    if fresh:
+        data = rng.integers(0, 256, total, dtype=np.uint8)
+    plains = [data[int(offs[i]) + po:int(offs[i]) + po + int(plen[i])].tobytes()
+              for i in range(n)]
+    for a in (seq, flags, picks, plen, lens, offs, data, flip, flip_at):
+        a.setflags(write=False)
+    return types.SimpleNamespace(
+        n=n, hash_alg=hash_alg, hl=hl, po=po, hkey=hkey, halt=halt, ekey=ekey, ealt=ealt,
+        no_cutoff=no_cutoff, rx_start=rx_start, cutoff=cutoff, seq=seq, flags=flags,
+        picks=picks, plen=plen, lens=lens, offs=offs, total=total, data=data,
+        plains=plains, flip=flip, flip_at=flip_at)
 
-    s = torch.cuda.Stream(device=dev)
-    d = _dev(data, dev)
-    d_flip = _dev(flip_at, dev)
-    d_seq, d_fl = _dev(_i32(seq), dev), _dev(_i32(flags), dev)
-    d_off, d_len = _dev(offs.astype(np.int64), dev), _dev(_i32(lens), dev)
-    d_plen = _dev(_i32(plen), dev)
+
+def chain_device(dev, c):
+    """The chain's inputs on the device; `d` is the buffer it works in."""
     groups = []
     for alt in (False, True):
-        idx = np.nonzero(picks == alt)[0]
-        groups.append((idx, _dev(idx.astype(np.int64), dev), halt if alt else hkey,
-                       ealt if alt else ekey))
-    torch.cuda.synchronize()                        # inputs are in place
-    tx_out = []
-    with torch.cuda.stream(s):
-        for idx, d_idx, hk, ek in groups:
-            m = len(idx)
-            g_seq, g_fl = d_seq[d_idx].contiguous(), d_fl[d_idx].contiguous()
-            g_off, g_len = d_off[d_idx].contiguous(), d_len[d_idx].contiguous()
-            g_plen = d_plen[d_idx].contiguous()
-            iv = torch.empty((m, 16), dtype=torch.uint8, device=dev)
-            _lib.check(L.net2_ph_to_iv_dev(g_seq.data_ptr(), g_fl.data_ptr(), m, 16,
-                                           iv.data_ptr(), s.cuda_stream))
-            eres, wire = cipher_burst.encrypt_burst(ek, hl, g_fl, iv, d, g_off, g_len,
-                                                    g_plen, stream=s)
-            ws = torch.empty(L.net2_packet_burst_workspace(m), dtype=torch.uint8,
-                             device=dev)
-            sres = torch.empty(m, dtype=torch.uint8, device=dev)
-            _lib.check(L.net2_packet_encode_burst(
-                hash_alg, hk, hl, 1, g_seq.data_ptr(), g_fl.data_ptr(), d.data_ptr(),
-                g_off.data_ptr(), wire.data_ptr(), m, sres.data_ptr(), ws.data_ptr(),
-                ws.numel(), s.cuda_stream))
-            tx_out.append((eres, wire, sres, ws))
-        sealed = d.clone()
-        d[d_flip] ^= 0x40
-        # RX
-        res = torch.full((n,), 9, dtype=torch.uint8, device=dev)
-        iv = torch.zeros((n, 16), dtype=torch.uint8, device=dev)
-        r_seq = torch.empty(n, dtype=torch.int32, device=dev)
-        r_fl = torch.empty(n, dtype=torch.int32, device=dev)
-        ws = torch.empty(L.net2_packet_burst_workspace(n), dtype=torch.uint8, device=dev)
-        kb, ab = ctypes.create_string_buffer(hkey, hl), ctypes.create_string_buffer(halt, hl)
-        ks = _lib.BurstRxKeys(hash_alg, ctypes.cast(kb, ctypes.c_void_p), hl, 1,
-                              ctypes.cast(ab, ctypes.c_void_p), hl, int(no_cutoff), cutoff,
-                              rx_start)
-        _lib.check(L.net2_packet_decode_burst_ck(
-            ctypes.byref(ks), 16, d.data_ptr(), d_off.data_ptr(), d_len.data_ptr(), n,
-            res.data_ptr(), iv.data_ptr(), r_seq.data_ptr(), r_fl.data_ptr(),
-            ws.data_ptr(), ws.numel(), s.cuda_stream))
-        out = torch.full((total,), SENTINEL, dtype=torch.uint8, device=dev)
-        res, out, got_plen = cipher_burst.decrypt_burst(
-            hash_alg, ekey, d, d_off, d_len, r_seq, r_fl, iv, res, alt_key=ealt,
-            alt_no_cutoff=no_cutoff, alt_cutoff=cutoff, rx_start=rx_start, out=out, stream=s)
-    s.synchronize()
+        idx = np.nonzero(c.picks == alt)[0]
+        groups.append((idx, _dev(idx.astype(np.int64), dev), c.halt if alt else c.hkey,
+                       c.ealt if alt else c.ekey))
+    return types.SimpleNamespace(
+        d=_dev(c.data, dev), d_flip=_dev(c.flip_at, dev), d_seq=_dev(_i32(c.seq), dev),
+        d_fl=_dev(_i32(c.flags), dev), d_off=_dev(c.offs.astype(np.int64), dev),
+        d_len=_dev(_i32(c.lens), dev), d_plen=_dev(_i32(c.plen), dev), groups=groups)
 
+
+def chain_body(dev, c, t, s):
+    """Every call of the chain on stream s, nothing synchronised: TX per key
+    set, the tamper step, RX.  Returns the outputs, and the host buffers of
+    the RX hash keys."""
+    from ilias_net2_amd import _lib, cipher_burst
+    L = _lib.lib()
+    n, hash_alg, hl, total = c.n, c.hash_alg, c.hl, c.total
+    hkey, halt, ekey, ealt = c.hkey, c.halt, c.ekey, c.ealt
+    no_cutoff, cutoff, rx_start = c.no_cutoff, c.cutoff, c.rx_start
+    d, d_flip, d_seq, d_fl = t.d, t.d_flip, t.d_seq, t.d_fl
+    d_off, d_len, d_plen = t.d_off, t.d_len, t.d_plen
+    tx_out = []
+    for idx, d_idx, hk, ek in t.groups:
+        m = len(idx)
+        g_seq, g_fl = d_seq[d_idx].contiguous(), d_fl[d_idx].contiguous()
+        g_off, g_len = d_off[d_idx].contiguous(), d_len[d_idx].contiguous()
+        g_plen = d_plen[d_idx].contiguous()
+        iv = torch.empty((m, 16), dtype=torch.uint8, device=dev)
+        _lib.check(L.net2_ph_to_iv_dev(g_seq.data_ptr(), g_fl.data_ptr(), m, 16,
+                                       iv.data_ptr(), s.cuda_stream))
+        eres, wire = cipher_burst.encrypt_burst(ek, hl, g_fl, iv, d, g_off, g_len,
+                                                g_plen, stream=s)
+        ws = torch.empty(L.net2_packet_burst_workspace(m), dtype=torch.uint8,
+                         device=dev)
+        sres = torch.empty(m, dtype=torch.uint8, device=dev)
+        _lib.check(L.net2_packet_encode_burst(
+            hash_alg, hk, hl, 1, g_seq.data_ptr(), g_fl.data_ptr(), d.data_ptr(),
+            g_off.data_ptr(), wire.data_ptr(), m, sres.data_ptr(), ws.data_ptr(),
+            ws.numel(), s.cuda_stream))
+        tx_out.append((eres, wire, sres, ws, (g_seq, g_fl, g_off, g_len, g_plen, iv)))
+    sealed = d.clone()
+    d[d_flip] ^= 0x40
+    # RX
+    res = torch.full((n,), 9, dtype=torch.uint8, device=dev)
+    iv = torch.zeros((n, 16), dtype=torch.uint8, device=dev)
+    r_seq = torch.empty(n, dtype=torch.int32, device=dev)
+    r_fl = torch.empty(n, dtype=torch.int32, device=dev)
+    ws = torch.empty(L.net2_packet_burst_workspace(n), dtype=torch.uint8, device=dev)
+    kb, ab = ctypes.create_string_buffer(hkey, hl), ctypes.create_string_buffer(halt, hl)
+    ks = _lib.BurstRxKeys(hash_alg, ctypes.cast(kb, ctypes.c_void_p), hl, 1,
+                          ctypes.cast(ab, ctypes.c_void_p), hl, int(no_cutoff), cutoff,
+                          rx_start)
+    _lib.check(L.net2_packet_decode_burst_ck(
+        ctypes.byref(ks), 16, d.data_ptr(), d_off.data_ptr(), d_len.data_ptr(), n,
+        res.data_ptr(), iv.data_ptr(), r_seq.data_ptr(), r_fl.data_ptr(),
+        ws.data_ptr(), ws.numel(), s.cuda_stream))
+    out = torch.full((total,), SENTINEL, dtype=torch.uint8, device=dev)
+    res, out, got_plen = cipher_burst.decrypt_burst(
+        hash_alg, ekey, d, d_off, d_len, r_seq, r_fl, iv, res, alt_key=ealt,
+        alt_no_cutoff=no_cutoff, alt_cutoff=cutoff, rx_start=rx_start, out=out, stream=s)
+    return types.SimpleNamespace(groups=t.groups, tx_out=tx_out, sealed=sealed, res=res,
+                                 out=out, got_plen=got_plen, keys=(kb, ab),
+                                 keep=(iv, r_seq, r_fl, ws))
+
+
+def chain_check(oracle_mod, c, o):
+    """What the chain left, against EVP and the oracle (the outputs are read
+    after the stream has finished)."""
+    n, hash_alg, po, total = c.n, c.hash_alg, c.po, c.total
+    ekey, ealt, seq, flags, picks = c.ekey, c.ealt, c.seq, c.flags, c.picks
+    plen, lens, offs, data, plains, flip = c.plen, c.lens, c.offs, c.data, c.plains, c.flip
+    groups, tx_out, sealed = o.groups, o.tx_out, o.sealed
+    res, out, got_plen = o.res, o.out, o.got_plen
     # the sealed datagrams are the oracle's over the helper-encrypted payloads
     ivs = oracle_mod.ph_to_iv_batch(seq, flags, 16)
     want = data.copy()
@@ -478,7 +542,7 @@ def _chain_on_one_stream(dev, oracle_mod, no_cutoff):
         ct = aes_ref.encrypt(ealt if picks[i] else ekey, ivs[i].tobytes(), plains[i])
         a = int(offs[i]) + po
         want[a:a + len(ct)] = np.frombuffer(ct, dtype=np.uint8)
-    for (idx, _, hk, _), (eres, wire, sres, _) in zip(groups, tx_out):
+    for (idx, _, hk, _), (eres, wire, sres, _, _) in zip(groups, tx_out):
         assert (eres.cpu().numpy() == OK).all() and (sres.cpu().numpy() == OK).all()
         assert np.array_equal(wire.cpu().numpy().view(np.uint32), lens[idx])
         r, sealed_ref = oracle_mod.packet_encode_batch(hash_alg, hk, True, seq[idx],
@@ -972,7 +1036,8 @@ def above_4gib_case():
         offs=offs, wins=wins, base=base, c_offs=c_offs, data=data, plains=plains)
 
 
-def test_chain_above_4gib(dev, oracle_mod):
+@pytest.mark.parametrize("form", list(HASH_FORMS))
+def test_chain_above_4gib(dev, oracle_mod, hash_form, form):
     """The whole chain (IVs, encrypt, seal, verify, decrypt) in place on one
     stream over a buffer of 2^32 + 2^16 bytes: a group of datagrams near
     offset 64, one packed from 2^32 - 700 on so that a datagram straddles
@@ -980,9 +1045,13 @@ def test_chain_above_4gib(dev, oracle_mod):
     straddling group ends past 2^32 + 5).  Every kernel takes 64-bit offsets;
     an offset cut to 32 bits would land in the first 64 KiB, which is
     compared as well, with 4 KiB on either side of every group.  Only the
-    windows used are ever written or read."""
+    windows used are ever written or read.  The hash bursts in each of their
+    forms (at the default limits 130 datagrams take the wave form alone):
+    hmac_kernel's burst modes, burst_prep_kernel and burst_final_kernel see
+    these offsets in the lane and binned forms, on prepared workspaces."""
     from ilias_net2_amd import _lib, cipher_burst
     L = _lib.lib()
+    hash_form(form)
     free, _ = torch.cuda.mem_get_info(dev)
     if free < (8 << 30):
         pytest.skip("needs 8 GiB of free device memory")
@@ -1023,6 +1092,8 @@ def test_chain_above_4gib(dev, oracle_mod):
                                                     g_plen, stream=s)
             ws = torch.empty(L.net2_packet_burst_workspace(m), dtype=torch.uint8,
                              device=dev)
+            _lib.check(L.net2_sha2_workspace_init(ws.data_ptr(), ws.numel(),
+                                                  s.cuda_stream))
             sres = torch.empty(m, dtype=torch.uint8, device=dev)
             _lib.check(L.net2_packet_encode_burst(
                 hash_alg, hk, hl, 1, g_seq.data_ptr(), g_fl.data_ptr(), big.data_ptr(),
@@ -1035,6 +1106,7 @@ def test_chain_above_4gib(dev, oracle_mod):
         r_seq = torch.empty(n, dtype=torch.int32, device=dev)
         r_fl = torch.empty(n, dtype=torch.int32, device=dev)
         ws = torch.empty(L.net2_packet_burst_workspace(n), dtype=torch.uint8, device=dev)
+        _lib.check(L.net2_sha2_workspace_init(ws.data_ptr(), ws.numel(), s.cuda_stream))
         kb, ab = ctypes.create_string_buffer(hkey, hl), ctypes.create_string_buffer(halt, hl)
         ks = _lib.BurstRxKeys(hash_alg, ctypes.cast(kb, ctypes.c_void_p), hl, 1,
                               ctypes.cast(ab, ctypes.c_void_p), hl, 0, cutoff, rx_start)

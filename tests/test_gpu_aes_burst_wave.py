@@ -24,6 +24,7 @@ import pytest
 
 import aes_ref
 import test_gpu_aes_burst as A
+from test_gpu_aes_burst import hash_form  # noqa: F401  (the hash bursts' form)
 import test_gpu_aes_burst_mc as M
 
 pytestmark = pytest.mark.gpu
@@ -118,8 +119,8 @@ def test_keys_need_not_outlive_the_call_wave_form(dev, oracle_mod, wave):
     A.test_keys_need_not_outlive_the_call(dev, oracle_mod)
 
 
-def test_chain_above_4gib_wave_form(dev, oracle_mod, wave):
-    A.test_chain_above_4gib(dev, oracle_mod)
+def test_chain_above_4gib_wave_form(dev, oracle_mod, wave, hash_form):
+    A.test_chain_above_4gib(dev, oracle_mod, hash_form, "wave")
 
 
 @pytest.mark.parametrize("in_place", [False, True])

@@ -12,8 +12,14 @@ geometry they claim and that the oracle refuses every flipped bit.
 The forms (net2_sha2_burst_limits): "lane" -- hmac_kernel, one lane per
 datagram in submission order; "binned" -- the same, visited in the
 length-binned order; "wave" -- burst_wave_kernel.
+
+The second half is the IV output (ph_iv_one): every IV length of B.IVLENS
+through the three RX entry points in every form, the IV array at unaligned
+addresses with guard bytes around it, d_iv = NULL, and net2_ph_to_iv_dev row
+by row.
 """
 import ctypes
+import types
 
 import numpy as np
 import pytest
@@ -80,16 +86,20 @@ def workspace(L, n, dev):
     return ws
 
 
-def check_rx(c, a, res, iv, seq, fl, sentinel):
+def check_rx(c, a, res, iv, seq, fl, sentinel, rows=None, due=None):
     """Codes, headers, the IVs of the OK rows, and every other IV row left
-    as it was."""
+    as it was.  rows: the expected IV rows at an IV length other than IVLEN
+    (default: the answers' own, a.rx_iv); due: the rows an IV is due to where
+    that is not every OK row (a connection without a cipher key)."""
     e = c.expect
     assert np.array_equal(res, a.rx_res), (e.name, np.nonzero(res != a.rx_res)[0][:8])
     known = e.rx_codes >= 0
     assert np.array_equal(res[known], e.rx_codes[known]), e.name
     assert np.array_equal(seq, a.rx_seq) and np.array_equal(fl, a.rx_fl), e.name
-    ok = a.rx_res == B.OK
-    assert np.array_equal(iv[ok], a.rx_iv[ok]), e.name
+    ok = a.rx_res == B.OK if due is None else due
+    rows = a.rx_iv if rows is None else rows
+    assert iv.shape == rows.shape, (e.name, iv.shape, rows.shape)
+    assert np.array_equal(iv[ok], rows[ok]), e.name
     if sentinel is not None:
         assert (iv[~ok] == sentinel).all(), e.name
 
@@ -302,3 +312,278 @@ def test_datagram_sign_verify(dev, oracle_mod, alg, binned):
         assert np.array_equal(got, a.verdict), (e.name, np.nonzero(got != a.verdict)[0][:8])
         if e.name.startswith("B1"):
             assert np.array_equal(got, (e.kinds != B.CONTROL).astype(np.uint8))
+
+
+# ---- the IV output: every length, every placement ----------------------------
+#
+# ph_iv_one (sha2_burst.h) takes a second SHA-256 round only above 32 bytes,
+# stores 16 bytes at a time only when the length is a multiple of 16 *and* the
+# row's address is 16-byte aligned (decided per lane), and otherwise runs a
+# byte loop; the wave forms derive the rows into LDS and copy them out
+# (bw_store_iv).  The expected rows are oracle.ph_to_iv_batch's, which
+# tests/test_burst_cases.py holds against hashlib at every length of B.IVLENS.
+
+GUARD = 64                  # sentinel bytes after (and `start` before) the rows
+CK_IVLENS = (1, 24, 33, 48, 64)
+
+
+def iv_rows(oracle_mod, seq, fl, ivlen):
+    return np.array(oracle_mod.ph_to_iv_batch(seq, fl, ivlen, nthreads=1)
+                    ).reshape(len(seq), ivlen)
+
+
+def head(c, a, m):
+    """The first m datagrams of a case and of its answers, for check_rx (the
+    datagrams of a burst are decoded independently of each other)."""
+    e = c.expect
+    c2 = c._replace(expect=types.SimpleNamespace(name=f"{e.name}[:{m}]", n=m,
+                                                 rx_codes=e.rx_codes[:m]))
+    a2 = types.SimpleNamespace(rx_res=a.rx_res[:m], rx_seq=a.rx_seq[:m],
+                               rx_fl=a.rx_fl[:m], rx_iv=a.rx_iv[:m])
+    return c2, a2
+
+
+def decode_rows(dev, c, a, ivlen, call, start=0, tail=GUARD, m=None, null_iv=False):
+    """One RX burst over the first m (default: all) datagrams of the case's
+    received bytes through `call(L, ivlen, d, o, ln, m, res, iv, seq, fl, ws,
+    ws_bytes, stream)` -- the C entry point, given device addresses -- with
+    the IV rows a slice of m * ivlen bytes that starts `start` bytes into an
+    allocation of SENTINEL bytes and ends `tail` bytes before its end.
+    Returns the host outputs, the whole allocation and the workspace's
+    binning statistics."""
+    from ilias_net2_amd import _lib
+    L = _lib.lib()
+    e = c.expect
+    m = e.n if m is None else m
+    st = torch.cuda.current_stream().cuda_stream
+    ws = workspace(L, m, dev)
+    d, o = _dev(a.rx, dev), _dev(c.offs[:m].view(np.int64), dev)
+    ln = _dev(e.rx_lens[:m].view(np.int32), dev)
+    res = torch.full((m,), 9, dtype=torch.uint8, device=dev)
+    room = torch.full((max(start + m * ivlen + tail, 1),), SENTINEL, dtype=torch.uint8,
+                      device=dev)
+    assert room.data_ptr() % 16 == 0
+    oseq = torch.full((m,), 7, dtype=torch.int32, device=dev)
+    ofl = torch.full((m,), 7, dtype=torch.int32, device=dev)
+    # (an empty slice has no address of its own: the array's address is given)
+    rc = call(L, ivlen, d.data_ptr(), o.data_ptr(), ln.data_ptr(), m, res.data_ptr(),
+              None if null_iv else room.data_ptr() + start, oseq.data_ptr(),
+              ofl.data_ptr(), ws.data_ptr(), ws.numel(), st)
+    assert rc == 0, (e.name, rc)
+    torch.cuda.synchronize()
+    got = room.cpu().numpy()
+    return types.SimpleNamespace(
+        res=res.cpu().numpy(), room=got,
+        iv=got[start:start + m * ivlen].reshape(m, ivlen),
+        before=got[:start], after=got[start + m * ivlen:],
+        seq=oseq.cpu().numpy().view(np.uint32), fl=ofl.cpu().numpy().view(np.uint32),
+        stats=_lib.workspace_stats(ws.data_ptr(), ws.numel()))
+
+
+def plain_call(alg, key):
+    """net2_packet_decode_burst under one key, the cipher set."""
+    def call(L, ivlen, d, o, ln, m, res, iv, seq, fl, ws, wsb, st):
+        return L.net2_packet_decode_burst(alg, key, B.HL[alg], 1, ivlen, d, o, ln, m,
+                                          res, iv, seq, fl, ws, wsb, st)
+    return call
+
+
+def ck_call(alg, key, alt):
+    """net2_packet_decode_burst_ck with an alternate key installed."""
+    from ilias_net2_amd import _lib
+    hl = B.HL[alg]
+
+    def call(L, ivlen, d, o, ln, m, res, iv, seq, fl, ws, wsb, st):
+        kb, ab = ctypes.create_string_buffer(key, hl), ctypes.create_string_buffer(alt, hl)
+        ks = _lib.BurstRxKeys(alg, ctypes.cast(kb, ctypes.c_void_p), hl, 1,
+                              ctypes.cast(ab, ctypes.c_void_p), hl, 1, 0, 0)
+        return L.net2_packet_decode_burst_ck(ctypes.byref(ks), ivlen, d, o, ln, m, res,
+                                             iv, seq, fl, ws, wsb, st)
+    return call
+
+
+def check_rows(c, a, g, rows, form, due=None):
+    """check_rx on decode_rows' outputs, the guard bytes around the rows, and
+    the form's binning statistics."""
+    check_rx(c, a, g.res, g.iv, g.seq, g.fl, SENTINEL, rows=rows, due=due)
+    assert (g.before == SENTINEL).all() and (g.after == SENTINEL).all(), c.expect.name
+    if form == "binned":
+        assert g.stats["binned"] >= 1 and g.stats["aborts"] == 0, g.stats
+        assert g.stats["mismatches"] == 0, g.stats
+    else:
+        assert g.stats["binned"] == 0, g.stats
+
+
+@pytest.mark.parametrize("form", list(FORMS))
+@pytest.mark.parametrize("alg", B.ALGS)
+@pytest.mark.parametrize("ivlen", B.IVLENS)
+def test_iv_lengths(dev, oracle_mod, limits, ivlen, alg, form):
+    """net2_packet_decode_burst at every IV length of B.IVLENS on the
+    every-bit case (OK, BAD, UNSAFE and header-flipped rows in every wave):
+    the OK rows are the oracle's, every other row and the bytes around the
+    array keep the sentinel; ivlen 0 with an array given writes no byte."""
+    limits(form)
+    c = B.B1(alg, 8, 100)
+    a = B.answers(oracle_mod, c)
+    g = decode_rows(dev, c, a, ivlen, plain_call(alg, a.keys[0]))
+    check_rows(c, a, g, iv_rows(oracle_mod, a.rx_seq, a.rx_fl, ivlen), form)
+    ok = a.rx_res == B.OK
+    assert ok.any() and (a.rx_res == B.BAD).any() and (a.rx_res == B.UNSAFE).any()
+    if ivlen == 0:
+        assert (g.room == SENTINEL).all()
+
+
+@pytest.mark.parametrize("form", ["lane", "wave"])
+@pytest.mark.parametrize("alg", B.ALGS)
+@pytest.mark.parametrize("ivlen", CK_IVLENS)
+def test_iv_lengths_alternate_key(dev, oracle_mod, limits, ivlen, alg, form):
+    """The same through net2_packet_decode_burst_ck during a key rollover
+    (odd datagrams under the alternate key)."""
+    limits(form)
+    c = B.B1(alg, 8, 100, altkey=True)
+    a = B.answers(oracle_mod, c)
+    assert a.alt
+    g = decode_rows(dev, c, a, ivlen, ck_call(alg, a.keys[0], a.keys[1]))
+    check_rows(c, a, g, iv_rows(oracle_mod, a.rx_seq, a.rx_fl, ivlen), form)
+
+
+_mc_answers = {}
+
+
+def mc_answers(oracle_mod, c, ivlen, K=3, plain=1):
+    """The oracle's decode of the case's received bytes with datagram i on
+    connection i % K; connection `plain` has no cipher set (enc_set false:
+    PH_ENCRYPTED is not demanded and no IV is due)."""
+    e = c.expect
+    tag = (e.name, ivlen, K, plain)
+    if tag in _mc_answers:
+        return _mc_answers[tag]
+    a = B.answers(oracle_mod, c, nconn=K)
+    res = np.full(e.n, 9, dtype=np.uint8)
+    iv = np.zeros((e.n, ivlen), dtype=np.uint8)
+    seq, fl = np.zeros(e.n, dtype=np.uint32), np.zeros(e.n, dtype=np.uint32)
+    due = np.zeros(e.n, dtype=bool)
+    for k in range(K):
+        idx = np.nonzero(a.group == k)[0]
+        r, v, s, f = oracle_mod.packet_decode_batch(
+            e.alg, a.keys[k], k != plain, ivlen, a.rx, c.offs[idx], e.rx_lens[idx],
+            nthreads=1)
+        res[idx], seq[idx], fl[idx] = r, s, f
+        iv[idx] = np.array(v).reshape(len(idx), ivlen)
+        due[idx] = (r == B.OK) & (k != plain) & ((f & B.PH_ENCRYPTED) != 0)
+    rows = iv_rows(oracle_mod, seq, fl, ivlen)
+    # the oracle's decode derives exactly the rows that are due
+    assert np.array_equal(iv[due], rows[due]) and not iv[~due].any()
+    out = types.SimpleNamespace(rx=a.rx, keys=a.keys, rx_res=res, rx_seq=seq, rx_fl=fl, rx_iv=rows,
+                   due=due, group=a.group)
+    _mc_answers[tag] = out
+    return out
+
+
+@pytest.mark.parametrize("form", list(FORMS))
+@pytest.mark.parametrize("alg", B.ALGS)
+@pytest.mark.parametrize("ivlen", B.IVLENS)
+def test_iv_lengths_many_connections(dev, oracle_mod, limits, ivlen, alg, form):
+    """net2_packet_decode_burst_mc, datagram i on connection i % 3, at every
+    IV length: connection 1 has no cipher set, so its OK rows keep the
+    sentinel like the refused rows of the other two."""
+    from ilias_net2_amd import conn_burst
+    limits(form)
+    K = 3
+    c = B.B1(alg, 8, 100)
+    a = mc_answers(oracle_mod, c, ivlen, K)
+    plain_ok = (a.rx_res == B.OK) & (a.group == 1)
+    assert plain_ok.sum() > 20 and not a.due[plain_ok].any() and a.due.sum() > 40
+    with conn_burst.KeyTable(alg, K) as tab:
+        for k in range(K):
+            tab.set_rx(k, a.keys[k], enc_set=(k != 1))
+        conn = _dev((np.arange(c.expect.n) % K).astype(np.int32), dev)
+
+        def call(L, ivlen, d, o, ln, m, res, iv, seq, fl, ws, wsb, st):
+            return L.net2_packet_decode_burst_mc(tab.ptr, conn.data_ptr(), ivlen, d, o, ln,
+                                                 m, res, iv, seq, fl, ws, wsb, st)
+        g = decode_rows(dev, c, a, ivlen, call)
+    check_rows(c, a, g, a.rx_iv, form, due=a.due)
+
+
+@pytest.mark.parametrize("form", list(FORMS))
+@pytest.mark.parametrize("alg", [4, 6])
+@pytest.mark.parametrize("ivlen", [16, 32, 48, 17])
+@pytest.mark.parametrize("start", [1, 4, 8])
+def test_iv_placement(dev, oracle_mod, limits, start, ivlen, alg, form):
+    """The IV array is a contiguous slice that starts 1, 4 or 8 bytes into
+    its allocation: no row (start 8 with ivlen 16: none at all) is 16-byte
+    aligned, so the 16-byte stores must not be taken, and the bytes before
+    and after the slice keep the sentinel."""
+    limits(form)
+    c = B.B1(alg, 8, 100)
+    a = B.answers(oracle_mod, c)
+    g = decode_rows(dev, c, a, ivlen, plain_call(alg, a.keys[0]), start=start)
+    assert len(g.before) == start and len(g.after) == GUARD
+    check_rows(c, a, g, iv_rows(oracle_mod, a.rx_seq, a.rx_fl, ivlen), form)
+
+
+@pytest.mark.parametrize("form", list(FORMS))
+def test_iv_array_ends_with_its_allocation(dev, oracle_mod, limits, form):
+    """ivlen 16 at start 0, the burst cut to a whole number of 512-byte
+    allocation units: the last row's last byte is the tensor's last."""
+    limits(form)
+    c = B.B1(6, 8, 100)
+    a = B.answers(oracle_mod, c)
+    m = c.expect.n - c.expect.n % 32
+    assert m > 512 and (m * IVLEN) % 512 == 0
+    c2, a2 = head(c, a, m)
+    g = decode_rows(dev, c, a, IVLEN, plain_call(6, a.keys[0]), tail=0, m=m)
+    assert len(g.room) == m * IVLEN
+    check_rows(c2, a2, g, None, form)
+
+
+@pytest.mark.parametrize("form", ["lane", "binned"])
+@pytest.mark.parametrize("alg", B.ALGS)
+def test_null_iv_array(dev, oracle_mod, limits, alg, form):
+    """d_iv = NULL with ivlen 16 in the single-connection lane and binned
+    forms: codes and headers are the full call's, no IV is derived."""
+    limits(form)
+    c = B.B1(alg, 8, 100)
+    a = B.answers(oracle_mod, c)
+    g = decode_rows(dev, c, a, IVLEN, plain_call(alg, a.keys[0]), null_iv=True)
+    assert np.array_equal(g.res, a.rx_res)
+    assert np.array_equal(g.seq, a.rx_seq) and np.array_equal(g.fl, a.rx_fl)
+    assert (g.room == SENTINEL).all()
+
+
+@pytest.fixture(scope="module")
+def iv_headers(dev):
+    rng = np.random.default_rng(1717)
+    n = 1001
+    seq = rng.integers(0, 2**32, n, dtype=np.uint64).astype(np.uint32)
+    fl = rng.integers(0, 2**32, n, dtype=np.uint64).astype(np.uint32)
+    return seq, fl, _dev(seq.view(np.int32), dev), _dev(fl.view(np.int32), dev)
+
+
+@pytest.mark.parametrize("start", [0, 1, 8])
+@pytest.mark.parametrize("ivlen", B.IVLENS)
+def test_ph_to_iv_dev_rows(dev, oracle_mod, iv_headers, ivlen, start):
+    """net2_ph_to_iv_dev over 1,001 random headers (four workgroups, the last
+    ragged): every row at every IV length, the output a slice at byte 0, 1
+    and 8 of its allocation with guard bytes around it; ivlen 0 writes
+    nothing; above 64 it is EINVAL."""
+    import errno
+    from ilias_net2_amd import _lib
+    L = _lib.lib()
+    seq, fl, ds, df = iv_headers
+    n = len(seq)
+    room = torch.full((start + n * ivlen + GUARD,), SENTINEL, dtype=torch.uint8,
+                      device=dev)
+    assert room.data_ptr() % 16 == 0
+    st = torch.cuda.current_stream().cuda_stream
+    assert L.net2_ph_to_iv_dev(ds.data_ptr(), df.data_ptr(), n, ivlen,
+                               room.data_ptr() + start, st) == 0
+    torch.cuda.synchronize()
+    got = room.cpu().numpy()
+    want = iv_rows(oracle_mod, seq, fl, ivlen)
+    rows = got[start:start + n * ivlen].reshape(n, ivlen)
+    assert np.array_equal(rows, want), np.nonzero((rows != want).any(axis=1))[0][:8]
+    assert (got[:start] == SENTINEL).all() and (got[start + n * ivlen:] == SENTINEL).all()
+    assert L.net2_ph_to_iv_dev(ds.data_ptr(), df.data_ptr(), n, 65,
+                               room.data_ptr() + start, st) == errno.EINVAL

@@ -13,6 +13,16 @@ BIN = os.path.join(ROOT, "tests", "c", "test_sign")
 LIB = os.path.join(ROOT, "ilias_net2_amd", "libnet2_sign.so")
 KEYS = [os.path.join(ROOT, "tests", "golden", "keys", f)
         for f in ("ecdsa_p521_priv.pem", "ecdsa_p521_pub.pem")]
+CSRC = os.path.join(ROOT, "ilias_net2_amd", "csrc")
+
+
+def _bin():
+    """The test program, which build() makes with the library; made here
+    (the same make target) where a tree has the library but not the
+    program, so the tests do not depend on what else lies under tests/."""
+    if not os.path.exists(BIN):
+        subprocess.run(["make", "-s", "-C", CSRC, BIN], check=True, timeout=600)
+    return BIN
 
 
 def _declared(hdr):
@@ -39,7 +49,7 @@ def test_sign_library_exports():
 
 def test_reference_sign_flow_cpu():
     """test/sign.c:57-185 restated: ECDSA on the host, no hashing."""
-    r = subprocess.run([BIN, *KEYS, "cpu"], capture_output=True, text=True,
+    r = subprocess.run([_bin(), *KEYS, "cpu"], capture_output=True, text=True,
                        timeout=120)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "PASS cpu-only" in r.stdout
@@ -50,7 +60,7 @@ def test_sign_and_signatures_gpu():
     """Fingerprint, signature create/validate single and batched: every
     digest from the GPU path, cross-checked by verifying with an
     OpenSSL-computed digest."""
-    r = subprocess.run([BIN, *KEYS], capture_output=True, text=True,
+    r = subprocess.run([_bin(), *KEYS], capture_output=True, text=True,
                        timeout=600)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "PASS (0 failures)" in r.stdout
