@@ -154,6 +154,9 @@ SIGNATURES = {
     # the decrypt bursts' two forms: the size threshold, launches by form
     "net2_aes_burst_limits": (ctypes.c_int, [ctypes.c_int64]),
     "net2_aes_burst_stats": (ctypes.c_int, [_c_u64p, _c_u64p]),
+    # the encrypt bursts' two forms: the size threshold, launches by form
+    "net2_aes_encrypt_limits": (ctypes.c_int, [ctypes.c_int64]),
+    "net2_aes_encrypt_stats": (ctypes.c_int, [_c_u64p, _c_u64p]),
     # the device key table and the bursts over many connections
     "net2_burst_keytab_create": (ctypes.c_int, [
         ctypes.c_int, ctypes.c_uint32, ctypes.POINTER(ctypes.c_void_p)]),

@@ -43,6 +43,22 @@ def stats() -> dict:
     return {"lane_launches": lane.value, "wave_launches": wave.value}
 
 
+def encrypt_limits(quad_max: int) -> None:
+    """``net2_aes_encrypt_limits``: the largest burst that ``encrypt_burst`` and
+    ``encrypt_burst_mc`` encrypt four lanes per datagram (0: never; < 0: the
+    default).  Process-wide; results do not depend on it, only the time."""
+    check(_lib.lib().net2_aes_encrypt_limits(quad_max), "net2_aes_encrypt_limits")
+
+
+def encrypt_stats() -> dict:
+    """``net2_aes_encrypt_stats``: this process's encrypt launches so far, by
+    form: ``{"lane_launches": ..., "quad_launches": ...}``."""
+    lane, quad = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    check(_lib.lib().net2_aes_encrypt_stats(ctypes.byref(lane), ctypes.byref(quad)),
+          "net2_aes_encrypt_stats")
+    return {"lane_launches": lane.value, "quad_launches": quad.value}
+
+
 def _cipher_keys(key: bytes, alt_key: Optional[bytes]):
     """struct net2_burst_cipher_keys and the buffers it points into."""
     kb = ctypes.create_string_buffer(bytes(key), max(len(key), 1))

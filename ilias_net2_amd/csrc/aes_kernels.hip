@@ -8,7 +8,8 @@
  * One lane per datagram, as in the hash bursts: on TX the CBC chain is serial
  * within a datagram anyway, and RX takes the same shape so both directions
  * share the block code (aes_device.h) and the tests.  Small RX bursts take
- * the wave form instead (one wave per datagram, further down).
+ * the wave form instead (one wave per datagram, further down), small TX
+ * bursts the quad form (four lanes per datagram, after it).
  *
  * What a lane does with its datagram -- the burst's arguments, the prep step
  * that settles what needs no cipher, the CBC chain of each direction, the
@@ -16,7 +17,8 @@
  * that the host tests run as it stands.  This file keeps what is device-only:
  * the LDS table and the round-key accessors, the ranking, the kernels (each
  * lane kernel: prep, rank, table, one call of its direction's chain under its
- * key source), the wave form, the table update and the launchers.
+ * key source), the wave form of RX, the quad form of TX, the table update and
+ * the launchers.
  *
  * LDS layout.  A workgroup is 256 lanes and holds one T-table (Te0 forward,
  * Td0 inverse) replicated 32 times: entry x for lane l is dword
@@ -45,6 +47,7 @@
 #include "aes_cbc.h"
 #include "aes_device.h"
 #include "aes_launch.h"
+#include "aes_quad.h"
 #include "aes_sched.h"
 #include "aes_tab.h"
 #include "aes_wave.h"
@@ -499,6 +502,171 @@ __global__ __launch_bounds__(AES_WG) void aes_cbc_decrypt_wave_kernel(
 }
 
 /*
+ * The quad form of TX, for small bursts (net2_aes_encrypt_limits): four
+ * adjacent lanes per datagram, one column of the state each -- 16 datagrams a
+ * wave, AES_QUADS a workgroup.  CBC encryption is serial from block to block,
+ * so the wave form above does not transfer; inside a block a round's four
+ * columns are independent, and with one lane per datagram a small burst lasts
+ * as long as 89 blocks of sixteen look-ups a round, one after the other.  Here
+ * a lane's chain is four look-ups a round, and the three columns it needs
+ * from its neighbours come by three DPP moves (quad_perm; no LDS, no
+ * barrier).  aes_quad.h has the schedule -- which column and which schedule
+ * words a lane owns, the word it contributes to a block, the steps of a
+ * block -- and this kernel follows it call by call.
+ *
+ * A DPP move reads its neighbours' registers as they are in that instruction,
+ * so all four lanes of a quad must be in the same control flow wherever one
+ * executes.  Everything that decides a quad's control flow is therefore a
+ * function of its datagram alone: the index, hence the end of the burst; the
+ * block count, which lane 0 of the quad works out (the lane form's
+ * encrypt_prep / encrypt_mc_prep, which settles what needs no cipher) and a
+ * quad_perm [0,0,0,0] makes known to the other three.  Quads of one wave
+ * differ in length and diverge from each other, never within themselves.
+ * What differs between the lanes of a quad is data only: the column, the
+ * addresses, the tail bytes below plen.
+ *
+ * The table is the lane form's, lane l on bank l & 31: a ds_read_b32 is served
+ * per half-wave of 32 lanes over 32 banks and every lane of a half-wave reads
+ * its own bank, so no lookup conflicts and the time of a lookup does not
+ * depend on key or data.  The table build ends in the kernel's only barrier
+ * and comes before anything that can end a lane.  Quad d of workgroup g takes
+ * datagrams (g * per + k) * AES_QUADS + d, k = 0 .. per - 1: the launch raises
+ * per with n as the wave form's does.
+ *
+ * Keys, two instances of the body.  One key: the schedule sits in the
+ * launch's arguments, is copied to LDS once per workgroup (published by the
+ * table build's barrier) and lane q picks its fifteen words from there.  _mc:
+ * lane q takes its fifteen words from the tx schedule of its datagram's table
+ * entry (ciphertab_ent: the index clamped before any address is formed).
+ * Either way they stay in VGPRs for all of a datagram's blocks.
+ *
+ * Lane q moves dword q of each block, a 4-byte access at byte alignment, and
+ * touches only bytes of its own datagram's payload: whole blocks below the
+ * last, in the last one the plaintext bytes below plen (read) and the whole
+ * block (written).
+ */
+constexpr int AES_QUADS = AES_WG / NET2_AES_QUAD_LANES;	/* datagrams per workgroup and step */
+
+template <bool MC> struct AesQuadArgs;
+template <> struct AesQuadArgs<false> {
+	AesBurstArgs b;
+	AesKeys<1> keys;
+	__device__ __forceinline__ const AesBurstArgs &burst() const { return b; }
+};
+template <> struct AesQuadArgs<true> {
+	AesMcArgs m;
+	__device__ __forceinline__ const AesBurstArgs &burst() const { return m.b; }
+};
+
+/* quad_perm's control word: lane q of every quad reads lane sel(q). */
+constexpr int quad_ctrl(uint32_t s0, uint32_t s1, uint32_t s2, uint32_t s3)
+{
+	return (int)(s0 | s1 << 2 | s2 << 4 | s3 << 6);
+}
+/* ... for the k-th input of a column (aes_quad_src), and for lane 0's value */
+constexpr int quad_ctrl_src(uint32_t k)
+{
+	return quad_ctrl(aes_quad_src(0, k), aes_quad_src(1, k), aes_quad_src(2, k),
+	    aes_quad_src(3, k));
+}
+constexpr int QUAD_FIRST = quad_ctrl(0, 0, 0, 0);
+
+/* v of the lane that CTRL names, within the calling lane's quad.  Every lane
+ * of the quad executes it together. */
+template <int CTRL>
+__device__ __forceinline__ uint32_t quad_perm(uint32_t v)
+{
+	return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, true);
+}
+
+/* The fifteen schedule words of lane q out of a 60-word schedule. */
+struct RkQuad {
+	uint32_t w[NET2_AES_QUAD_KEYWORDS];
+	__device__ __forceinline__ RkQuad(const uint32_t *p, uint32_t q)
+	{
+#pragma unroll
+		for (int r = 0; r < NET2_AES_QUAD_KEYWORDS; r++)
+			w[r] = p[aes_quad_rk(r, q)];
+	}
+};
+
+/*
+ * Slot i, nb >= 1 blocks, by the calling quad (all four lanes call; i and nb
+ * are the same in them): the chain of aes_quad.h, the next block's word loaded
+ * before the current one goes through the rounds.  q: the lane's column, K:
+ * its schedule words.
+ */
+__device__ __forceinline__ void encrypt_by_quad(const AesBurstArgs &a,
+    uint64_t i, uint32_t nb, const LdsTab &T, const RkQuad &K, uint32_t q)
+{
+	uint8_t *p = a.out + a.offsets[i] + payload_at(a.flags[i], a.hashlen);
+	const uint32_t plen = a.plen[i];
+	uint32_t chain = aes_quad_ld(a.iv + NET2_AES_BLOCK * i, q);
+	uint32_t cur = aes_quad_word(p, plen, nb, 0, q);
+
+	for (uint32_t j = 0; j < nb; j++) {
+		uint32_t nx = 0;
+		if (j + 1 < nb)
+			nx = aes_quad_word(p, plen, nb, j + 1, q);
+		uint32_t s = aes_quad_enter(chain, cur, K.w[0]);
+#pragma unroll
+		for (int r = 1; r <= NET2_AES_ROUNDS; r++) {
+			const uint32_t s1 = quad_perm<quad_ctrl_src(1)>(s);
+			const uint32_t s2 = quad_perm<quad_ctrl_src(2)>(s);
+			const uint32_t s3 = quad_perm<quad_ctrl_src(3)>(s);
+			s = aes_quad_round(T, r, s, s1, s2, s3, K.w[r]);
+		}
+		aes_quad_st(p + 16 * (uint64_t)j, q, s);
+		chain = s;
+		cur = nx;
+	}
+}
+
+template <bool MC>
+__global__ __launch_bounds__(AES_WG) void aes_cbc_encrypt_quad_kernel(
+    const AesQuadArgs<MC> w, const uint32_t per)
+{
+	__shared__ uint32_t tab[256 * AES_REP];
+	__shared__ uint32_t rks[MC ? 4 : 64];
+
+	const AesBurstArgs &a = w.burst();
+	const uint32_t t = threadIdx.x;
+	if constexpr (!MC) {
+		if (t < NET2_AES_RKWORDS)
+			rks[t] = w.keys.k[0].w[t];
+	}
+	/* the one barrier (it publishes rks as well): before any lane can end */
+	aes_build_table<false>(tab);
+
+	const uint32_t q = aes_quad_col(t), quad = aes_quad_of(t);
+	const LdsTab T = { tab + (t & (AES_REP - 1)) };
+	for (uint32_t k = 0; k < per; k++) {
+		const uint64_t i = ((uint64_t)blockIdx.x * per + k) * AES_QUADS + quad;
+		if (i >= a.n)
+			break;
+		/* lane 0 settles what needs no cipher, as a lane of the lane form */
+		uint32_t nb = 0;
+		if (q == 0) {
+			if constexpr (MC)
+				nb = encrypt_mc_prep(w.m, i);
+			else
+				nb = encrypt_prep(a, i);
+		}
+		nb = quad_perm<QUAD_FIRST>(nb);
+		if (nb == 0)
+			continue;
+		if constexpr (MC) {
+			bool in;
+			const RkQuad K(ciphertab_ent(w.m, i, &in)->enc, q);
+			encrypt_by_quad(a, i, nb, T, K, q);
+		} else {
+			const RkQuad K(rks, q);
+			encrypt_by_quad(a, i, nb, T, K, q);
+		}
+	}
+}
+
+/*
  * One slot's update (net2_burst_ciphertab_set_rx / _set_tx / _clear): the new
  * entry arrives by value and one wave stores it, 16 bytes per lane (the
  * argument is read with constant indices only and selected per lane: a
@@ -635,6 +803,21 @@ uint32_t wave_per(uint64_t n)
 dim3 wave_grid(uint64_t n, uint32_t per)
 {
 	const uint64_t step = (uint64_t)AES_WAVES * per;
+	return dim3((unsigned)((n + step - 1) / step));
+}
+
+/* The quad form's datagrams per quad (the kernel's per) and grid, by the wave
+ * form's rule: AES_QUADS datagrams per workgroup and step. */
+uint32_t quad_per(uint64_t n)
+{
+	const uint64_t per = (n + AES_QUADS * AES_WAVE_GRID - 1) /
+	    (AES_QUADS * AES_WAVE_GRID);
+	return (uint32_t)(per < 1 ? 1 : per > AES_WAVE_PER_MAX ? AES_WAVE_PER_MAX : per);
+}
+
+dim3 quad_grid(uint64_t n, uint32_t per)
+{
+	const uint64_t step = (uint64_t)AES_QUADS * per;
 	return dim3((unsigned)((n + step - 1) / step));
 }
 
@@ -790,5 +973,41 @@ hipError_t net2_launch_aes_encrypt_mc(const AesTabArgs &kt, uint32_t hashlen,
 	    lens, plen, n, result, wire_len), kt);
 	hipLaunchKernelGGL(aes_cbc_encrypt_mc_kernel, lane_grid(n), dim3(AES_WG), 0,
 	    s, m);
+	return hipGetLastError();
+}
+
+/* ---- the quad form of the encrypt launches ---------------------------------- */
+
+hipError_t net2_launch_aes_encrypt_quad(const uint8_t *key, uint32_t hashlen,
+    const uint32_t *flags, const uint8_t *iv, uint8_t *base,
+    const uint64_t *offsets, const uint32_t *lens, const uint32_t *plen,
+    uint64_t n, uint8_t *result, uint32_t *wire_len, hipStream_t s)
+{
+	if (n == 0)
+		return hipSuccess;
+	AesQuadArgs<false> w;
+	w.b = encrypt_args(hashlen, flags, iv, base, offsets, lens, plen, n, result,
+	    wire_len);
+	aes256_enc_schedule(key, &w.keys.k[0]);
+	const uint32_t per = quad_per(n);
+	hipLaunchKernelGGL(aes_cbc_encrypt_quad_kernel<false>, quad_grid(n, per),
+	    dim3(AES_WG), 0, s, w, per);
+	key_wipe(&w.keys, sizeof(w.keys));
+	return hipGetLastError();
+}
+
+hipError_t net2_launch_aes_encrypt_mc_quad(const AesTabArgs &kt,
+    uint32_t hashlen, const uint32_t *flags, const uint8_t *iv, uint8_t *base,
+    const uint64_t *offsets, const uint32_t *lens, const uint32_t *plen,
+    uint64_t n, uint8_t *result, uint32_t *wire_len, hipStream_t s)
+{
+	if (n == 0)
+		return hipSuccess;
+	AesQuadArgs<true> w = {};
+	w.m = mc_args(encrypt_args(hashlen, flags, iv, base, offsets, lens, plen, n,
+	    result, wire_len), kt);
+	const uint32_t per = quad_per(n);
+	hipLaunchKernelGGL(aes_cbc_encrypt_quad_kernel<true>, quad_grid(n, per),
+	    dim3(AES_WG), 0, s, w, per);
 	return hipGetLastError();
 }

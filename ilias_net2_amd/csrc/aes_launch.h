@@ -95,4 +95,19 @@ hipError_t net2_launch_aes_decrypt_mc_wave(const AesTabArgs &kt,
     const uint32_t *flags, const uint8_t *iv, uint8_t *result, uint8_t *out,
     uint32_t *plen, hipStream_t s);
 
+/*
+ * The quad form of the two encrypt launches, for small bursts: four lanes per
+ * datagram, one column of the state each (aes_quad.h), in place of one lane
+ * per datagram.  Same arguments, same codes, lengths and output bytes; which
+ * form a call takes is net2_dgram.cpp's choice (net2_aes_encrypt_limits).
+ */
+hipError_t net2_launch_aes_encrypt_quad(const uint8_t *key, uint32_t hashlen,
+    const uint32_t *flags, const uint8_t *iv, uint8_t *base,
+    const uint64_t *offsets, const uint32_t *lens, const uint32_t *plen,
+    uint64_t n, uint8_t *result, uint32_t *wire_len, hipStream_t s);
+hipError_t net2_launch_aes_encrypt_mc_quad(const AesTabArgs &kt,
+    uint32_t hashlen, const uint32_t *flags, const uint8_t *iv, uint8_t *base,
+    const uint64_t *offsets, const uint32_t *lens, const uint32_t *plen,
+    uint64_t n, uint8_t *result, uint32_t *wire_len, hipStream_t s);
+
 #endif /* NET2_AES_LAUNCH_H */

@@ -175,14 +175,17 @@ int check_cipher_keys(const struct net2_burst_cipher_keys *ck)
 	return 0;
 }
 
-/* net2_sha2_burst_limits' two thresholds, net2_aes_burst_limits' one */
+/* net2_sha2_burst_limits' two thresholds, net2_aes_burst_limits' one,
+ * net2_aes_encrypt_limits' one */
 FormKnob g_burst_wave_max{"NET2_BURST_WAVE_MAX"};
 FormKnob g_burst_bin_min{"NET2_BURST_BIN_MIN"};
 FormKnob g_aes_wave_max{"NET2_AES_WAVE_MAX"};
+FormKnob g_aes_quad_max{"NET2_AES_QUAD_MAX"};
 
 /* net2_sha2_burst_stats' counts (keyed hash-burst launches) and
- * net2_aes_burst_stats' (decrypt launches) */
-FormCounts g_burst_launches, g_aes_launches;
+ * net2_aes_burst_stats' (decrypt launches); net2_aes_encrypt_stats' (encrypt
+ * launches: `wave` counts the quad form) */
+FormCounts g_burst_launches, g_aes_launches, g_aes_tx_launches;
 
 /*
  * The binning workspace a burst's HMAC kernel is given: below the binning
@@ -430,7 +433,35 @@ bool aes_wave_form(uint64_t n)
 	return n <= g_aes_wave_max.get(AES_WAVE_MAX_DEFAULT);
 }
 
+/*
+ * The largest burst encrypted in the quad form (four lanes per datagram), by
+ * the same rule from tools/aes_burst_sizes.py --direction tx (DESIGN.md
+ * 5.5.7, profiles/aes_burst_quad/sizes.jsonl): 188 against 275 us there, 97 to
+ * 104 against 241 to 258 us up to 16,384 datagrams; at 262,144 one lane per
+ * datagram wins, 436 against 696 us.
+ */
+constexpr uint64_t AES_QUAD_MAX_DEFAULT = 65536;
+
+/* Whether an encrypt burst of n takes the quad form. */
+bool aes_quad_form(uint64_t n)
+{
+	return n <= g_aes_quad_max.get(AES_QUAD_MAX_DEFAULT);
+}
+
 }	/* namespace */
+
+NET2_EXPORT int net2_aes_encrypt_limits(int64_t quad_max)
+{
+	g_aes_quad_max.set(quad_max);
+	return 0;
+}
+
+NET2_EXPORT int net2_aes_encrypt_stats(uint64_t *lane_launches,
+    uint64_t *quad_launches)
+{
+	g_aes_tx_launches.read(lane_launches, quad_launches);
+	return 0;
+}
 
 NET2_EXPORT int net2_aes_burst_limits(int64_t wave_max)
 {
@@ -500,9 +531,13 @@ NET2_EXPORT int net2_packet_encrypt_burst(
 		return EINVAL;
 	if (int rc = check_current_device())
 		return rc;
-	HIP_TRY(net2_launch_aes_encrypt((const uint8_t *)ck->enc_key, hashlen,
-	    d_flags, (const uint8_t *)d_iv, (uint8_t *)d_base, d_offsets, d_lens,
-	    d_plen, n, d_result, d_wire_len, (hipStream_t)stream));
+	/* a small burst: four lanes per datagram (results are the same) */
+	const bool quad = aes_quad_form(n);
+	HIP_TRY((quad ? net2_launch_aes_encrypt_quad : net2_launch_aes_encrypt)(
+	    (const uint8_t *)ck->enc_key, hashlen, d_flags, (const uint8_t *)d_iv,
+	    (uint8_t *)d_base, d_offsets, d_lens, d_plen, n, d_result, d_wire_len,
+	    (hipStream_t)stream));
+	g_aes_tx_launches.count(quad);
 	return 0;
 }
 
@@ -887,8 +922,10 @@ NET2_EXPORT int net2_packet_encrypt_burst_mc(
 	if (int rc = check_table_device(tab->device))
 		return rc;
 	const AesTabArgs kt = { d_conn, tab->ents, tab->slots };
-	HIP_TRY(net2_launch_aes_encrypt_mc(kt, hashlen, d_flags,
-	    (const uint8_t *)d_iv, (uint8_t *)d_base, d_offsets, d_lens, d_plen, n,
-	    d_result, d_wire_len, (hipStream_t)stream));
+	const bool quad = aes_quad_form(n);
+	HIP_TRY((quad ? net2_launch_aes_encrypt_mc_quad : net2_launch_aes_encrypt_mc)(
+	    kt, hashlen, d_flags, (const uint8_t *)d_iv, (uint8_t *)d_base, d_offsets,
+	    d_lens, d_plen, n, d_result, d_wire_len, (hipStream_t)stream));
+	g_aes_tx_launches.count(quad);
 	return 0;
 }

@@ -260,7 +260,8 @@ int net2_packet_encrypt_burst(const struct net2_burst_cipher_keys *ck,
  * measured crossover, 65,536 datagrams on an MI355X, or NET2_AES_WAVE_MAX
  * when set in the environment at first use).  Results do not depend on it --
  * codes, lengths and every output byte are the same in both forms -- only the
- * time does.  The encrypt bursts have one form.  Always 0; needs no device.
+ * time does.  The encrypt bursts have a threshold of their own
+ * (net2_aes_encrypt_limits).  Always 0; needs no device.
  */
 int net2_aes_burst_limits(int64_t wave_max);
 
@@ -270,6 +271,26 @@ int net2_aes_burst_limits(int64_t wave_max);
  * or one refused by its argument checks launches nothing.  Always 0.
  */
 int net2_aes_burst_stats(uint64_t *lane_launches, uint64_t *wave_launches);
+
+/*
+ * Size threshold of the encrypt bursts, process-wide (diagnostics, tests and
+ * A/B runs), for net2_packet_encrypt_burst and net2_packet_encrypt_burst_mc
+ * alike: quad_max is the largest burst encrypted four lanes per datagram, one
+ * column of the AES state each (0: never); a larger burst is encrypted one
+ * lane per datagram.  A value < 0 restores the default (the measured
+ * crossover on an MI355X, DESIGN.md 5.5.7, or NET2_AES_QUAD_MAX when set in
+ * the environment at first use).  Results do not depend on it -- codes,
+ * d_wire_len and every output byte are the same in both forms -- only the
+ * time does.  Always 0; needs no device.
+ */
+int net2_aes_encrypt_limits(int64_t quad_max);
+
+/*
+ * Encrypt launches of this process so far, by form (either pointer may be
+ * NULL): the only way to tell which form a call took.  A call with n == 0
+ * or one refused by its argument checks launches nothing.  Always 0.
+ */
+int net2_aes_encrypt_stats(uint64_t *lane_launches, uint64_t *quad_launches);
 
 /*
  * Keyed bursts over many connections.  The reference terminates many
