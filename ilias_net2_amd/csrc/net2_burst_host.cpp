@@ -5,12 +5,6 @@
  */
 #include "net2_host.h"
 
-/* keyed host bursts of at most this many datagrams read their datagrams and
- * metadata through the host mapping (enqueue_burst_steps) */
-#ifndef NET2_BURST_ZC_MAX
-#define NET2_BURST_ZC_MAX 16384
-#endif
-
 void BurstSlot::release()
 {
 	drop_host(h_in);
@@ -19,7 +13,8 @@ void BurstSlot::release()
 	drop_dev(d_in);
 	drop_dev(d_ws);
 	drop_dev(d_meta);
-	cap_in = cap_n = 0;
+	drop_dev(d_aux);
+	cap_in = cap_n = cap_aux = 0;
 }
 
 int BurstSlot::reserve(size_t in, size_t n)
@@ -32,29 +27,27 @@ int BurstSlot::reserve(size_t in, size_t n)
 	HIP_TRY(hipHostMalloc((void **)&h_in, in, hipHostMallocDefault));
 	HIP_TRY(hipHostMalloc((void **)&h_out, out_bytes(n),
 	    hipHostMallocDefault));
-	HIP_TRY(hipHostMalloc((void **)&h_meta, meta_bytes(n, true),
+	HIP_TRY(hipHostMalloc((void **)&h_meta, mc_meta_bytes(n),
 	    hipHostMallocDefault));
 	HIP_TRY(hipMalloc((void **)&d_in, in));
-	HIP_TRY(hipMalloc((void **)&d_meta, meta_bytes(n, true)));
+	HIP_TRY(hipMalloc((void **)&d_meta, mc_meta_bytes(n)));
 	HIP_TRY(hipMalloc((void **)&d_ws, burst_layout(n, nullptr, nullptr)));
 	return grown(d_ws, in, n);
 }
 
-namespace {
-
-/*
- * Where the kernels store a chunk's output of `bytes` bytes bound for the
- * caller's `user` (its chunk slice): straight into it through its device
- * mapping when it is page-locked, else into `stage` (the slot's pinned
- * results, mapped) -- then *copy is set and the caller copies it over once
- * the chunk is done.
- */
-uint8_t *out_ptr(void *user, bool user_pinned, uint8_t *stage, bool *copy)
+int BurstSlot::reserve_aux(size_t ivlen)
 {
-	uint8_t *dp = user_pinned ? mapped(user) : nullptr;
-	*copy = dp == nullptr;
-	return dp != nullptr ? dp : mapped(stage);
+	const size_t need = Aux::bytes(cap_n, ivlen);
+	if (need <= cap_aux)
+		return 0;
+	drop_dev(d_aux);
+	cap_aux = 0;
+	HIP_TRY(hipMalloc((void **)&d_aux, need));
+	cap_aux = need;
+	return 0;
 }
+
+namespace {
 
 /* The pinned state of each caller buffer of a host burst (looked up once). */
 struct BurstPins {

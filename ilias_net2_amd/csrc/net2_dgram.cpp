@@ -427,11 +427,15 @@ namespace {
  */
 constexpr uint64_t AES_WAVE_MAX_DEFAULT = 65536;
 
+}	/* namespace */
+
 /* Whether a decrypt burst of n takes the wave form. */
 bool aes_wave_form(uint64_t n)
 {
 	return n <= g_aes_wave_max.get(AES_WAVE_MAX_DEFAULT);
 }
+
+namespace {
 
 /*
  * The largest burst encrypted in the quad form (four lanes per datagram), by
@@ -442,13 +446,13 @@ bool aes_wave_form(uint64_t n)
  */
 constexpr uint64_t AES_QUAD_MAX_DEFAULT = 65536;
 
+}	/* namespace */
+
 /* Whether an encrypt burst of n takes the quad form. */
 bool aes_quad_form(uint64_t n)
 {
 	return n <= g_aes_quad_max.get(AES_QUAD_MAX_DEFAULT);
 }
-
-}	/* namespace */
 
 NET2_EXPORT int net2_aes_encrypt_limits(int64_t quad_max)
 {
@@ -556,8 +560,6 @@ struct net2_burst_keytab {
 	Net2KeyEnt *ents;
 };
 
-namespace {
-
 /* Arguments first (by the caller), then: a usable device, and the table's. */
 int check_table_device(int device)
 {
@@ -568,6 +570,8 @@ int check_table_device(int device)
 		return ENODEV;
 	return cur == device ? 0 : EINVAL;
 }
+
+namespace {
 
 int check_keytab_device(const struct net2_burst_keytab *tab)
 {
@@ -685,20 +689,24 @@ NET2_EXPORT int net2_burst_keytab_clear(struct net2_burst_keytab *tab,
 	return 0;
 }
 
-NET2_EXPORT int net2_packet_decode_burst_mc(const struct net2_burst_keytab *tab,
-    const uint32_t *d_conn, uint32_t ivlen, const void *d_base,
-    const uint64_t *d_offsets, const uint32_t *d_lens, uint64_t n,
-    uint8_t *d_result, void *d_iv, uint32_t *d_seq, uint32_t *d_flags,
-    void *d_ws, size_t ws_bytes, void *stream)
+int keytab_device(const struct net2_burst_keytab *tab)
 {
-	int rc = check_burst_mc_args(tab, d_conn, ivlen, d_base, d_offsets,
-	    d_lens, n, d_result, d_ws, ws_bytes,
-	    (d_seq == nullptr) == (d_flags == nullptr));
-	if (rc != 0 || n == 0)
-		return rc;
-	hipStream_t s = (hipStream_t)stream;
+	return tab->device;
+}
+
+int keytab_hash_alg(const struct net2_burst_keytab *tab)
+{
+	return tab->hash_alg;
+}
+
+/* net2_packet_decode_burst_mc's launches, the arguments checked. */
+int decode_burst_mc(const struct net2_burst_keytab *tab, const uint32_t *d_conn,
+    uint32_t ivlen, const void *d_base, const uint64_t *d_offsets,
+    const uint32_t *d_lens, uint64_t n, uint8_t *d_result, void *d_iv,
+    uint32_t *d_seq, uint32_t *d_flags, void *d_ws, hipStream_t s, bool wave)
+{
 	const KeyTabArgs kt = { d_conn, tab->ents, tab->slots };
-	if (n <= net2_burst_wave_max()) {
+	if (wave) {
 		/* a small burst: 1 to 16 datagrams per workgroup; codes, headers
 		 * and IVs stored by that one launch, the workspace not touched */
 		BurstArgs rx = {};
@@ -730,6 +738,51 @@ NET2_EXPORT int net2_packet_decode_burst_mc(const struct net2_burst_keytab *tab,
 	return 0;
 }
 
+NET2_EXPORT int net2_packet_decode_burst_mc(const struct net2_burst_keytab *tab,
+    const uint32_t *d_conn, uint32_t ivlen, const void *d_base,
+    const uint64_t *d_offsets, const uint32_t *d_lens, uint64_t n,
+    uint8_t *d_result, void *d_iv, uint32_t *d_seq, uint32_t *d_flags,
+    void *d_ws, size_t ws_bytes, void *stream)
+{
+	int rc = check_burst_mc_args(tab, d_conn, ivlen, d_base, d_offsets,
+	    d_lens, n, d_result, d_ws, ws_bytes,
+	    (d_seq == nullptr) == (d_flags == nullptr));
+	if (rc != 0 || n == 0)
+		return rc;
+	return decode_burst_mc(tab, d_conn, ivlen, d_base, d_offsets, d_lens, n,
+	    d_result, d_iv, d_seq, d_flags, d_ws, (hipStream_t)stream,
+	    n <= net2_burst_wave_max());
+}
+
+/* net2_packet_encode_burst_mc's launches, the arguments checked.  seal_to:
+ * as encode_burst's (null: the datagrams are sealed in d_base). */
+int encode_burst_mc(const struct net2_burst_keytab *tab, const uint32_t *d_conn,
+    const uint32_t *d_seq, const uint32_t *d_flags, void *d_base,
+    const uint64_t *d_offsets, const uint32_t *d_lens, uint64_t n,
+    uint8_t *d_result, void *d_ws, hipStream_t stream, bool wave,
+    uint8_t *seal_to)
+{
+	uint8_t *const out = seal_to != nullptr ? seal_to : (uint8_t *)d_base;
+	BurstArgs tx = {};
+	tx.seq = const_cast<uint32_t *>(d_seq);
+	tx.flags = const_cast<uint32_t *>(d_flags);
+	tx.status = d_result;		/* the TX code is final in the kernel */
+	const KeyTabArgs kt = { d_conn, tab->ents, tab->slots };
+	if (wave) {
+		/* a small burst: 1 to 16 datagrams per workgroup */
+		HIP_TRY(net2_launch_burst_wave_mc(tab->hash_alg, kt,
+		    (const uint8_t *)d_base, d_offsets, d_lens, n, tx, d_result,
+		    nullptr, 0, out, NET2_HMAC_MODE_BURST_TX, stream));
+		return burst_launched(true);
+	}
+	BurstWs w;
+	burst_layout(n, (uint8_t *)d_ws, &w);
+	HIP_TRY(net2_launch_hmac_mc(tab->hash_alg, kt, (const uint8_t *)d_base,
+	    d_offsets, d_lens, n, out, burst_bins(n, w.bin), stream,
+	    NET2_HMAC_MODE_BURST_TX, tx));
+	return burst_launched(false);
+}
+
 NET2_EXPORT int net2_packet_encode_burst_mc(const struct net2_burst_keytab *tab,
     const uint32_t *d_conn, const uint32_t *d_seq, const uint32_t *d_flags,
     void *d_base, const uint64_t *d_offsets, const uint32_t *d_lens,
@@ -739,25 +792,9 @@ NET2_EXPORT int net2_packet_encode_burst_mc(const struct net2_burst_keytab *tab,
 	    d_result, d_ws, ws_bytes, d_seq != nullptr && d_flags != nullptr);
 	if (rc != 0 || n == 0)
 		return rc;
-	BurstArgs tx = {};
-	tx.seq = const_cast<uint32_t *>(d_seq);
-	tx.flags = const_cast<uint32_t *>(d_flags);
-	tx.status = d_result;		/* the TX code is final in the kernel */
-	const KeyTabArgs kt = { d_conn, tab->ents, tab->slots };
-	if (n <= net2_burst_wave_max()) {
-		/* a small burst: 1 to 16 datagrams per workgroup */
-		HIP_TRY(net2_launch_burst_wave_mc(tab->hash_alg, kt,
-		    (const uint8_t *)d_base, d_offsets, d_lens, n, tx, d_result,
-		    nullptr, 0, (uint8_t *)d_base, NET2_HMAC_MODE_BURST_TX,
-		    (hipStream_t)stream));
-		return burst_launched(true);
-	}
-	BurstWs w;
-	burst_layout(n, (uint8_t *)d_ws, &w);
-	HIP_TRY(net2_launch_hmac_mc(tab->hash_alg, kt, (const uint8_t *)d_base,
-	    d_offsets, d_lens, n, (uint8_t *)d_base, burst_bins(n, w.bin),
-	    (hipStream_t)stream, NET2_HMAC_MODE_BURST_TX, tx));
-	return burst_launched(false);
+	return encode_burst_mc(tab, d_conn, d_seq, d_flags, d_base, d_offsets,
+	    d_lens, n, d_result, d_ws, (hipStream_t)stream,
+	    n <= net2_burst_wave_max(), nullptr);
 }
 
 /* ---- the cipher under per-connection keys: the device cipher-key table ---- */
@@ -877,6 +914,41 @@ static bool digest_hashlen(uint32_t hashlen)
 	return hashlen == 0 || hashlen == 32 || hashlen == 48 || hashlen == 64;
 }
 
+int ciphertab_device(const struct net2_burst_ciphertab *tab)
+{
+	return tab->device;
+}
+
+/* net2_packet_decrypt_burst_mc's launch, the arguments checked. */
+int decrypt_burst_mc(const struct net2_burst_ciphertab *tab,
+    const uint32_t *d_conn, uint32_t hashlen, const void *d_base,
+    const uint64_t *d_offsets, const uint32_t *d_lens, uint64_t n,
+    const uint32_t *d_seq, const uint32_t *d_flags, const void *d_iv,
+    uint8_t *d_result, void *d_out, uint32_t *d_plen, hipStream_t s, bool wave)
+{
+	const AesTabArgs kt = { d_conn, tab->ents, tab->slots };
+	HIP_TRY((wave ? net2_launch_aes_decrypt_mc_wave : net2_launch_aes_decrypt_mc)(
+	    kt, hashlen, (const uint8_t *)d_base, d_offsets, d_lens, n, d_seq,
+	    d_flags, (const uint8_t *)d_iv, d_result, (uint8_t *)d_out, d_plen, s));
+	g_aes_launches.count(wave);
+	return 0;
+}
+
+/* net2_packet_encrypt_burst_mc's launch, the arguments checked. */
+int encrypt_burst_mc(const struct net2_burst_ciphertab *tab,
+    const uint32_t *d_conn, uint32_t hashlen, const uint32_t *d_flags,
+    const void *d_iv, void *d_base, const uint64_t *d_offsets,
+    const uint32_t *d_lens, const uint32_t *d_plen, uint64_t n,
+    uint8_t *d_result, uint32_t *d_wire_len, hipStream_t s, bool quad)
+{
+	const AesTabArgs kt = { d_conn, tab->ents, tab->slots };
+	HIP_TRY((quad ? net2_launch_aes_encrypt_mc_quad : net2_launch_aes_encrypt_mc)(
+	    kt, hashlen, d_flags, (const uint8_t *)d_iv, (uint8_t *)d_base, d_offsets,
+	    d_lens, d_plen, n, d_result, d_wire_len, s));
+	g_aes_tx_launches.count(quad);
+	return 0;
+}
+
 NET2_EXPORT int net2_packet_decrypt_burst_mc(
     const struct net2_burst_ciphertab *tab, const uint32_t *d_conn,
     uint32_t hashlen, const void *d_base, const uint64_t *d_offsets,
@@ -895,14 +967,9 @@ NET2_EXPORT int net2_packet_decrypt_burst_mc(
 		return EINVAL;
 	if (int rc = check_table_device(tab->device))
 		return rc;
-	const AesTabArgs kt = { d_conn, tab->ents, tab->slots };
-	const bool wave = aes_wave_form(n);
-	HIP_TRY((wave ? net2_launch_aes_decrypt_mc_wave : net2_launch_aes_decrypt_mc)(
-	    kt, hashlen, (const uint8_t *)d_base, d_offsets, d_lens, n, d_seq,
-	    d_flags, (const uint8_t *)d_iv, d_result, (uint8_t *)d_out, d_plen,
-	    (hipStream_t)stream));
-	g_aes_launches.count(wave);
-	return 0;
+	return decrypt_burst_mc(tab, d_conn, hashlen, d_base, d_offsets, d_lens, n,
+	    d_seq, d_flags, d_iv, d_result, d_out, d_plen, (hipStream_t)stream,
+	    aes_wave_form(n));
 }
 
 NET2_EXPORT int net2_packet_encrypt_burst_mc(
@@ -921,11 +988,7 @@ NET2_EXPORT int net2_packet_encrypt_burst_mc(
 		return EINVAL;
 	if (int rc = check_table_device(tab->device))
 		return rc;
-	const AesTabArgs kt = { d_conn, tab->ents, tab->slots };
-	const bool quad = aes_quad_form(n);
-	HIP_TRY((quad ? net2_launch_aes_encrypt_mc_quad : net2_launch_aes_encrypt_mc)(
-	    kt, hashlen, d_flags, (const uint8_t *)d_iv, (uint8_t *)d_base, d_offsets,
-	    d_lens, d_plen, n, d_result, d_wire_len, (hipStream_t)stream));
-	g_aes_tx_launches.count(quad);
-	return 0;
+	return encrypt_burst_mc(tab, d_conn, hashlen, d_flags, d_iv, d_base,
+	    d_offsets, d_lens, d_plen, n, d_result, d_wire_len,
+	    (hipStream_t)stream, aes_quad_form(n));
 }

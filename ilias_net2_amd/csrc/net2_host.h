@@ -1,6 +1,7 @@
 /*
  * net2_host.h -- internal: what the host units behind the C ABI share
- * (net2_runtime, net2_batch, net2_single, net2_dgram, net2_burst_host .cpp).
+ * (net2_runtime, net2_batch, net2_single, net2_dgram, net2_burst_host,
+ * net2_burst_mc_host .cpp).
  * Host orchestration only: argument checks with errno-style returns (the
  * reference maps hash failures to ENOMEM / NET2_P{EN,DE}CODE_RESOURCE,
  * types/signature.n2t:93-95, types/packet.n2t:246-249), device discovery,
@@ -193,6 +194,20 @@ inline uint8_t *mapped(const void *p)
 	return nullptr;
 }
 
+/*
+ * Where the kernels store a chunk's output of `bytes` bytes bound for the
+ * caller's `user` (its chunk slice): straight into it through its device
+ * mapping when it is page-locked, else into `stage` (the slot's pinned
+ * results, mapped) -- then *copy is set and the caller copies it over once
+ * the chunk is done.
+ */
+inline uint8_t *out_ptr(void *user, bool user_pinned, uint8_t *stage, bool *copy)
+{
+	uint8_t *dp = user_pinned ? mapped(user) : nullptr;
+	*copy = dp == nullptr;
+	return dp != nullptr ? dp : mapped(stage);
+}
+
 /* ---- per-device staging for the host-memory paths ------------------------ */
 
 template <class T> void drop_host(T *&p) { if (p) (void)hipHostFree(p); p = nullptr; }
@@ -237,24 +252,54 @@ struct BatchSlot : Slot {
 struct BurstSlot : Slot {
 	uint8_t *h_in = nullptr, *h_out = nullptr;
 	/* a chunk's per-datagram metadata, one block so it is one copy:
-	 * offsets (8 n), lengths (4 n), TX headers (8 n) -- see Meta */
+	 * offsets (8 n), lengths (4 n), TX headers (8 n); over many connections
+	 * also the slots (4 n) and TX plaintext lengths (4 n) -- see Meta */
 	uint8_t *h_meta = nullptr;
 	uint8_t *d_in = nullptr, *d_ws = nullptr, *d_meta = nullptr;
+	/* bursts over many connections: a chunk's per-datagram results in device
+	 * memory (Aux), where the cipher step reads what the hash step left;
+	 * allocated by the first such burst (reserve_aux) */
+	uint8_t *d_aux = nullptr;
+	size_t cap_aux = 0;
 
 	/* The metadata arrays of an n-datagram chunk inside a meta block. */
 	struct Meta {
 		uint64_t *off;
-		uint32_t *len, *hdr;
+		uint32_t *len, *hdr, *conn, *plen;
 		Meta(uint8_t *m, size_t n) : off((uint64_t *)m),
-		    len((uint32_t *)(m + 8 * n)), hdr((uint32_t *)(m + 12 * n)) {}
+		    len((uint32_t *)(m + 8 * n)), hdr((uint32_t *)(m + 12 * n)),
+		    conn((uint32_t *)(m + 20 * n)), plen((uint32_t *)(m + 24 * n)) {}
 	};
 	static size_t meta_bytes(size_t n, bool tx) { return n * (tx ? 20 : 12); }
+	static size_t mc_meta_bytes(size_t n) { return n * 28; }
 	/* results staged per datagram: RX code + IV (<= 64) + header; TX code
-	 * + record (hash field + header, <= 80) */
+	 * + record (hash field + header, <= 80); over many connections an Aux */
 	static size_t out_bytes(size_t n) { return n * 81 + 256; }
+
+	/* The per-datagram results of an n-datagram chunk over many connections,
+	 * every array 16-byte aligned: in d_aux, and staged in h_out (at most
+	 * 78 n + 96 bytes, within out_bytes).  len: RX plaintext lengths, TX
+	 * wire lengths; enc: the TX cipher step's codes. */
+	struct Aux {
+		uint8_t *res, *enc;
+		uint32_t *seq, *flags, *len;
+		uint8_t *iv;
+		Aux(uint8_t *b, size_t n) : res(b), enc(b + a16z(n)),
+		    seq((uint32_t *)(b + 2 * a16z(n))),
+		    flags((uint32_t *)(b + 2 * a16z(n) + a16z(4 * n))),
+		    len((uint32_t *)(b + 2 * a16z(n) + 2 * a16z(4 * n))),
+		    iv(b + 2 * a16z(n) + 3 * a16z(4 * n)) {}
+		static size_t a16z(size_t x) { return (x + 15) & ~(size_t)15; }
+		static size_t bytes(size_t n, size_t ivlen)
+		{
+			return 2 * a16z(n) + 3 * a16z(4 * n) + a16z(n * ivlen);
+		}
+	};
 
 	void release();
 	int reserve(size_t in, size_t n);
+	/* after reserve: d_aux for cap_n datagrams with IVs of ivlen bytes */
+	int reserve_aux(size_t ivlen);
 };
 
 /* A device's host-side state.  The pipelines hold different locks: a batch and
@@ -265,6 +310,9 @@ struct DeviceCtx {
 	BatchSlot slot[2];
 	std::mutex burst_mu;	/* one host burst per device at a time */
 	BurstSlot burst_slot[2];
+	/* under burst_mu: what a host burst over many connections records on the
+	 * caller's table stream and its chunks' streams wait for */
+	hipEvent_t tables_ev = nullptr;
 	/* net2_sha2_numa_stats: slices run, and those whose thread was on
 	 * the device's NUMA node when it finished */
 	std::atomic<uint64_t> slices{0}, slices_on_node{0};
@@ -361,6 +409,12 @@ struct FormCounts {
  * never), else net2_burst_wave_default(). */
 uint64_t net2_burst_wave_max(void);
 
+/* keyed host bursts of at most this many datagrams read their datagrams and
+ * metadata through the host mapping (enqueue_burst_steps) */
+#ifndef NET2_BURST_ZC_MAX
+#define NET2_BURST_ZC_MAX 16384
+#endif
+
 /* ---- the burst steps (net2_dgram.cpp) ------------------------------------- */
 
 inline size_t a16(size_t x) { return (x + 15) & ~(size_t)15; }
@@ -382,6 +436,42 @@ int encode_burst(int hash_alg, const void *hash_key, size_t hash_keylen,
     void *d_base, const uint64_t *d_offsets, const uint32_t *d_lens,
     uint64_t n, uint8_t *d_result, void *d_ws, hipStream_t s, bool wave,
     uint8_t *rec, bool bin = true, uint8_t *seal_to = nullptr);
+
+/*
+ * The same over many connections: the launches of net2_packet_{decode,encode}_
+ * burst_mc and net2_packet_{decrypt,encrypt}_burst_mc on device-visible
+ * memory, the arguments already checked.  The form is the caller's, decided
+ * once per chunk: wave from net2_burst_wave_max(), the cipher's from
+ * aes_wave_form(n) (decrypt) and aes_quad_form(n) (encrypt).  seal_to as
+ * encode_burst's.
+ */
+struct net2_burst_keytab;
+struct net2_burst_ciphertab;
+int keytab_device(const struct net2_burst_keytab *tab);
+int keytab_hash_alg(const struct net2_burst_keytab *tab);
+int ciphertab_device(const struct net2_burst_ciphertab *tab);
+/* Arguments first (by the caller), then: a usable device, and the table's. */
+int check_table_device(int device);
+bool aes_wave_form(uint64_t n);
+bool aes_quad_form(uint64_t n);
+int decode_burst_mc(const struct net2_burst_keytab *tab, const uint32_t *d_conn,
+    uint32_t ivlen, const void *d_base, const uint64_t *d_offsets,
+    const uint32_t *d_lens, uint64_t n, uint8_t *d_result, void *d_iv,
+    uint32_t *d_seq, uint32_t *d_flags, void *d_ws, hipStream_t s, bool wave);
+int encode_burst_mc(const struct net2_burst_keytab *tab, const uint32_t *d_conn,
+    const uint32_t *d_seq, const uint32_t *d_flags, void *d_base,
+    const uint64_t *d_offsets, const uint32_t *d_lens, uint64_t n,
+    uint8_t *d_result, void *d_ws, hipStream_t s, bool wave, uint8_t *seal_to);
+int decrypt_burst_mc(const struct net2_burst_ciphertab *tab,
+    const uint32_t *d_conn, uint32_t hashlen, const void *d_base,
+    const uint64_t *d_offsets, const uint32_t *d_lens, uint64_t n,
+    const uint32_t *d_seq, const uint32_t *d_flags, const void *d_iv,
+    uint8_t *d_result, void *d_out, uint32_t *d_plen, hipStream_t s, bool wave);
+int encrypt_burst_mc(const struct net2_burst_ciphertab *tab,
+    const uint32_t *d_conn, uint32_t hashlen, const uint32_t *d_flags,
+    const void *d_iv, void *d_base, const uint64_t *d_offsets,
+    const uint32_t *d_lens, const uint32_t *d_plen, uint64_t n,
+    uint8_t *d_result, uint32_t *d_wire_len, hipStream_t s, bool quad);
 
 /* What every burst entry checks once its keys are accepted: the IV length,
  * then -- of a burst that is not empty -- the arrays. */

@@ -369,8 +369,8 @@ int net2_burst_keytab_clear(struct net2_burst_keytab *tab, uint32_t slot,
  * read from the table by every workgroup, and does not touch the workspace
  * (which is required and checked all the same); a larger one is hashed one
  * datagram per lane, and bin_min applies.  Results do not depend on the
- * form; net2_sha2_burst_stats tells which one a call took.  Only the _host
- * pipelines remain single-connection.
+ * form; net2_sha2_burst_stats tells which one a call took.  The host form
+ * is net2_packet_{decode,encode}_burst_mc_host below.
  * EINVAL also when the calling thread's device is not the table's.
  */
 int net2_packet_decode_burst_mc(const struct net2_burst_keytab *tab,
@@ -500,6 +500,75 @@ int net2_packet_encode_burst_host(int hash_alg, const void *hash_key,
     size_t hash_keylen, int enc_alg, const uint32_t *seq,
     const uint32_t *flags, void *base, const uint64_t *offsets,
     const uint32_t *lens, uint64_t n, uint8_t *result, int max_devices);
+
+/*
+ * Host-memory bursts over many connections, with the payload cipher: what a
+ * receive loop takes off one shared, encrypted UDP socket (datagrams in host
+ * memory, of many connections, encrypted) in one synchronous call, and the
+ * send side of the same loop.  `tab` (and `ctab`) are the device tables above;
+ * table_stream is a stream of their device (NULL: the null stream); every
+ * other pointer is host memory, each array page-locked or pageable on its own.
+ * conn[i] is the slot of datagram i in both tables.  When a call returns every
+ * output is complete and nothing reads or writes the caller's memory any more.
+ *
+ * The results are those of the device-resident calls run on one stream over
+ * the same bytes, bit for bit:
+ *   RX: net2_packet_decode_burst_mc(tab, conn, ivlen, ...), then, with ctab,
+ *   net2_packet_decrypt_burst_mc(ctab, conn, hashlen of tab's row, ..., out,
+ *   plen).  result, iv (may be NULL), seq / flags (both or neither) and plen
+ *   are what that sequence leaves.  The first plen[i] bytes at out +
+ *   offsets[i] + po(i) of a decrypted datagram are its plaintext; what follows
+ *   them within that datagram's own bytes of `out` is unspecified, and no
+ *   other byte of `out` changes value.  out == base decrypts in place; any
+ *   other `out` must not overlap the burst.
+ *   TX: with ctab, net2_ph_to_iv_dev(seq, flags, n, 16, ...) and
+ *   net2_packet_encrypt_burst_mc(ctab, conn, hashlen, ..., plen, ..., wire_len)
+ *   -- slot i = base[offsets[i] .. + lens[i]) holding plen[i] plaintext bytes
+ *   at po(i) -- then net2_packet_encode_burst_mc with wire_len as its lengths.
+ *   result[i] is the cipher step's code where that is not NET2_PENCODE_OK,
+ *   else the hash step's; every byte of the caller's buffer is as the sequence
+ *   leaves the device copy (bytes between the slots keep their value).
+ *   ctab == NULL: the hash step alone -- the host forms of
+ *   net2_packet_{decode,encode}_burst_mc.  lens are the datagram lengths; RX
+ *   does not look at out and plen, TX not at plen and wire_len (all may be
+ *   NULL), and ivlen is any length up to 64.
+ *
+ * The call runs on the tables' device, which must be the calling thread's
+ * current device (it still is afterwards); tables are per device, so there is
+ * no max_devices and no sharding.  The datagrams go through the host bursts'
+ * pipeline: 64 MiB chunks, two in flight, copied as they lie from one dense
+ * page-locked allocation and packed into pinned staging otherwise; one host
+ * burst -- of either kind -- runs per device at a time.  The forms of the
+ * steps are those of the device calls, decided per chunk under
+ * net2_sha2_burst_limits, net2_aes_burst_limits and net2_aes_encrypt_limits
+ * and counted in their *_stats.
+ *
+ * Table updates queued on table_stream before the call are seen by it: the
+ * call records one event there and its own streams wait for it (no host
+ * synchronisation), so the tables' "ordered in the stream" property holds for
+ * table_stream.  Updates on any other stream must have completed.
+ *
+ * 0; EINVAL -- all before any device work, in this order: tab NULL; ivlen > 64;
+ * then for n > 0 a NULL base, offsets, lens or result, or n > UINT32_MAX; conn
+ * NULL; RX seq / flags not given together, TX either missing; with ctab: ivlen
+ * not 16, RX out or plen NULL, TX plen or wire_len NULL, or tables of two
+ * devices -- then ENODEV (no usable current device), EINVAL (the current device
+ * is not the tables'), ENOMEM or EIO (then some results may be unset, but what
+ * the chunks before the failed one delivered is complete).  n == 0 is 0 and
+ * touches nothing.
+ */
+int net2_packet_decode_burst_mc_host(const struct net2_burst_keytab *tab,
+    const struct net2_burst_ciphertab *ctab /* NULL: hash step only */,
+    const uint32_t *conn, uint32_t ivlen, const void *base,
+    const uint64_t *offsets, const uint32_t *lens, uint64_t n,
+    uint8_t *result, void *iv, uint32_t *seq, uint32_t *flags,
+    void *out, uint32_t *plen, void *table_stream);
+int net2_packet_encode_burst_mc_host(const struct net2_burst_keytab *tab,
+    const struct net2_burst_ciphertab *ctab /* NULL: hash step only */,
+    const uint32_t *conn, const uint32_t *seq, const uint32_t *flags,
+    void *base, const uint64_t *offsets, const uint32_t *lens,
+    const uint32_t *plen, uint64_t n, uint8_t *result, uint32_t *wire_len,
+    void *table_stream);
 
 #ifdef __cplusplus
 }
