@@ -55,6 +55,22 @@ class BurstCipherKeys(ctypes.Structure):
                 ("alt_enc_keylen", ctypes.c_size_t)]
 
 
+TAB_CLEAR, TAB_RX, TAB_TX = 0, 1, 2     # NET2_BURST_TAB_* (include/net2/packet.h)
+
+
+class BurstKeytabOp(ctypes.Structure):
+    """struct net2_burst_keytab_op (include/net2/packet.h)."""
+    _fields_ = [("slot", ctypes.c_uint32), ("op", ctypes.c_uint32),
+                ("rx", BurstRxKeys), ("tx_key", ctypes.c_void_p),
+                ("tx_keylen", ctypes.c_size_t), ("tx_enc_alg", ctypes.c_int)]
+
+
+class BurstCiphertabOp(ctypes.Structure):
+    """struct net2_burst_ciphertab_op (include/net2/packet.h)."""
+    _fields_ = [("slot", ctypes.c_uint32), ("op", ctypes.c_uint32),
+                ("rx", BurstRxKeys), ("ck", BurstCipherKeys)]
+
+
 class BinStats(ctypes.Structure):
     """struct net2_bin_stats (include/net2/sha2_batch.h)."""
     _fields_ = [("prepared", ctypes.c_uint32), ("binned", ctypes.c_uint32),
@@ -197,6 +213,20 @@ SIGNATURES = {
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
         ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p]),
+    # bulk updates of the two tables (one launch per ops_per_launch ops, the
+    # keys prepared on the device), their knob and counters, fingerprints
+    "net2_burst_keytab_update": (ctypes.c_int, [
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "net2_burst_ciphertab_update": (ctypes.c_int, [
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "net2_burst_tab_limits": (ctypes.c_int, [ctypes.c_int64]),
+    "net2_burst_tab_stats": (ctypes.c_int, [_c_u64p, _c_u64p]),
+    "net2_burst_keytab_fingerprint": (ctypes.c_int, [
+        ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
+        ctypes.c_void_p]),
+    "net2_burst_ciphertab_fingerprint": (ctypes.c_int, [
+        ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
         ctypes.c_void_p]),
     "net2_packet_decode_burst_host": (ctypes.c_int, [
         ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,

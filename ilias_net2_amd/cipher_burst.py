@@ -160,6 +160,27 @@ def encrypt_burst(key: bytes, hashlen: int, flags, iv, data, offsets, lens,
 NOCONN = 5          # NET2_PBURST_NOCONN
 
 
+# The ops of CipherTable.update: plain tuples (kind, slot, keyword arguments),
+# made by constructors that mirror set_rx / set_tx / clear.
+def rx_op(slot: int, key: bytes, hash_alg: int = 0,
+          alt_key: Optional[bytes] = None, alt_no_cutoff: bool = False,
+          alt_cutoff: int = 0, rx_start: int = 0):
+    """``CipherTable.set_rx(slot, key, ...)`` as an op of ``update``."""
+    return (_lib.TAB_RX, slot, dict(key=key, hash_alg=hash_alg, alt_key=alt_key,
+                                    alt_no_cutoff=alt_no_cutoff,
+                                    alt_cutoff=alt_cutoff, rx_start=rx_start))
+
+
+def tx_op(slot: int, key: bytes):
+    """``CipherTable.set_tx(slot, key)`` as an op of ``update``."""
+    return (_lib.TAB_TX, slot, dict(key=key))
+
+
+def clear_op(slot: int):
+    """``CipherTable.clear(slot)`` as an op of ``update``."""
+    return (_lib.TAB_CLEAR, slot, {})
+
+
 class CipherTable:
     """A device cipher-key table of ``slots`` connections (AES-256-CBC), on
     ``device`` (default: torch's current device): ``struct
@@ -224,6 +245,49 @@ class CipherTable:
             check(_lib.lib().net2_burst_ciphertab_clear(
                 self.ptr, slot, self._stream(stream)),
                 "net2_burst_ciphertab_clear")
+
+    def build_ops(self, ops):
+        """``ops`` (``rx_op`` / ``tx_op`` / ``clear_op``) as the array
+        ``net2_burst_ciphertab_update`` takes, and the key buffers it points
+        into: ``(array, buffers)``."""
+        arr = (_lib.BurstCiphertabOp * max(len(ops), 1))()
+        keep = []
+        for o, (kind, slot, kw) in zip(arr, ops):
+            o.slot, o.op = slot, kind
+            if kind == _lib.TAB_RX:
+                ck, bufs = _cipher_keys(kw["key"], kw["alt_key"])
+                keep.append(bufs)
+                o.ck = ck
+                o.rx = _lib.BurstRxKeys(
+                    kw["hash_alg"], None, 0, _lib.ENC_AES256, ck.alt_enc_key, 0,
+                    int(bool(kw["alt_no_cutoff"])), kw["alt_cutoff"] & 0xffffffff,
+                    kw["rx_start"] & 0xffffffff)
+            elif kind == _lib.TAB_TX:
+                ck, bufs = _cipher_keys(kw["key"], None)
+                keep.append(bufs)
+                o.ck = ck
+        return arr, keep
+
+    def update(self, ops, stream=None) -> None:
+        """Many slots in one call (``net2_burst_ciphertab_update``): ``ops``
+        is a list of ``rx_op`` / ``tx_op`` / ``clear_op``, applied in order;
+        the table ends as the per-slot calls in that order would leave it.
+        All or nothing: a bad op raises and nothing is enqueued."""
+        import torch
+        ops = list(ops)
+        arr, keep = self.build_ops(ops)
+        with torch.cuda.device(self.device):
+            rc = _lib.lib().net2_burst_ciphertab_update(
+                self.ptr, arr, len(ops), self._stream(stream))
+        del keep
+        check(rc, "net2_burst_ciphertab_update")
+
+    def fingerprints(self, stream=None):
+        """The SHA-256 of every entry, a (slots, 32) uint8 CUDA tensor
+        (``net2_burst_ciphertab_fingerprint``)."""
+        from .conn_burst import _fingerprints
+        return _fingerprints(_lib.lib().net2_burst_ciphertab_fingerprint,
+                             "net2_burst_ciphertab_fingerprint", self, stream)
 
     def close(self) -> None:
         if self._tab:

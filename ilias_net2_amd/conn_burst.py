@@ -21,6 +21,59 @@ from .batch import _launch_stream, _need
 NOCONN = 5          # NET2_PBURST_NOCONN
 
 
+# The ops of KeyTable.update: plain tuples (kind, slot, keyword arguments),
+# made by constructors that mirror set_rx / set_tx / clear.
+def rx_op(slot: int, key: bytes, enc_set: bool = False,
+          alt_key: Optional[bytes] = None, alt_no_cutoff: bool = False,
+          alt_cutoff: int = 0, rx_start: int = 0):
+    """``KeyTable.set_rx(slot, key, ...)`` as an op of ``KeyTable.update``."""
+    return (_lib.TAB_RX, slot, dict(key=key, enc_set=enc_set, alt_key=alt_key,
+                                    alt_no_cutoff=alt_no_cutoff,
+                                    alt_cutoff=alt_cutoff, rx_start=rx_start))
+
+
+def tx_op(slot: int, key: bytes, enc_set: bool = False):
+    """``KeyTable.set_tx(slot, key, ...)`` as an op of ``KeyTable.update``."""
+    return (_lib.TAB_TX, slot, dict(key=key, enc_set=enc_set))
+
+
+def clear_op(slot: int):
+    """``clear(slot)`` as an op of ``update`` (either table)."""
+    return (_lib.TAB_CLEAR, slot, {})
+
+
+def tab_limits(ops_per_launch: int) -> None:
+    """``net2_burst_tab_limits``: the most ops one launch of a bulk update
+    takes (< 0: the default, 65,536).  A test knob; results do not depend on
+    it."""
+    check(_lib.lib().net2_burst_tab_limits(ops_per_launch), "net2_burst_tab_limits")
+
+
+def tab_stats():
+    """``net2_burst_tab_stats``: this process's table-update launches so far
+    as ``(slot, bulk)`` -- those of the per-slot calls and those of the bulk
+    updates, both tables.  Host state; needs no device."""
+    slot, bulk = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    check(_lib.lib().net2_burst_tab_stats(ctypes.byref(slot), ctypes.byref(bulk)),
+          "net2_burst_tab_stats")
+    return slot.value, bulk.value
+
+
+def _key_buf(key: bytes):
+    return ctypes.create_string_buffer(bytes(key), max(len(key), 1))
+
+
+def _fingerprints(fn, what, table, stream):
+    """(slots, 32) uint8 CUDA tensor: the SHA-256 of every entry."""
+    import torch
+    s = _launch_stream(stream, table.device)
+    with torch.cuda.stream(s):
+        out = torch.empty((table.slots, 32), dtype=torch.uint8, device=table.device)
+    with torch.cuda.device(table.device):
+        check(fn(table.ptr, 0, table.slots, out.data_ptr(), s.cuda_stream), what)
+    return out
+
+
 class KeyTable:
     """A device key table of ``slots`` connections under one HMAC row
     (4..6), on ``device`` (default: torch's current device).  Updates are
@@ -84,6 +137,54 @@ class KeyTable:
             check(_lib.lib().net2_burst_keytab_clear(
                 self.ptr, slot, self._stream(stream)),
                 "net2_burst_keytab_clear")
+
+    def build_ops(self, ops):
+        """``ops`` (``rx_op`` / ``tx_op`` / ``clear_op``) as the array
+        ``net2_burst_keytab_update`` takes, and the key buffers it points
+        into: ``(array, buffers)``."""
+        arr = (_lib.BurstKeytabOp * max(len(ops), 1))()
+        keep = []
+        for o, (kind, slot, kw) in zip(arr, ops):
+            o.slot, o.op = slot, kind
+            if kind == _lib.TAB_RX:
+                kb = _key_buf(kw["key"])
+                ab = None if kw["alt_key"] is None else _key_buf(kw["alt_key"])
+                keep += [kb, ab]
+                o.rx = _lib.BurstRxKeys(
+                    self.hash_alg, ctypes.cast(kb, ctypes.c_void_p),
+                    len(kw["key"]), int(bool(kw["enc_set"])),
+                    None if ab is None else ctypes.cast(ab, ctypes.c_void_p),
+                    0 if ab is None else len(kw["alt_key"]),
+                    int(bool(kw["alt_no_cutoff"])), kw["alt_cutoff"] & 0xffffffff,
+                    kw["rx_start"] & 0xffffffff)
+            elif kind == _lib.TAB_TX:
+                kb = _key_buf(kw["key"])
+                keep.append(kb)
+                o.tx_key = ctypes.cast(kb, ctypes.c_void_p)
+                o.tx_keylen = len(kw["key"])
+                o.tx_enc_alg = int(bool(kw["enc_set"]))
+        return arr, keep
+
+    def update(self, ops, stream=None) -> None:
+        """Many slots in one call (``net2_burst_keytab_update``): ``ops`` is
+        a list of ``rx_op`` / ``tx_op`` / ``clear_op``, applied in order; the
+        table ends as the per-slot calls in that order would leave it.  All
+        or nothing: a bad op raises and nothing is enqueued."""
+        import torch
+        ops = list(ops)
+        arr, keep = self.build_ops(ops)
+        with torch.cuda.device(self.device):
+            rc = _lib.lib().net2_burst_keytab_update(
+                self.ptr, arr, len(ops), self._stream(stream))
+        del keep
+        check(rc, "net2_burst_keytab_update")
+
+    def fingerprints(self, stream=None):
+        """The SHA-256 of every entry, a (slots, 32) uint8 CUDA tensor
+        (``net2_burst_keytab_fingerprint``): equal for two tables that hold
+        the same keys and state."""
+        return _fingerprints(_lib.lib().net2_burst_keytab_fingerprint,
+                             "net2_burst_keytab_fingerprint", self, stream)
 
     def close(self) -> None:
         if self._tab:

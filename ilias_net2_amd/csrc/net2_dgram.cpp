@@ -138,6 +138,19 @@ size_t burst_layout(uint64_t n, uint8_t *base, BurstWs *w)
 	return at;
 }
 
+/* The cipher calls (net2_host.h): aes256 with a 32-byte key, and as long an alternate key
+ * or none */
+int check_cipher_keys(const struct net2_burst_cipher_keys *ck)
+{
+	if (ck == nullptr || ck->enc_alg != NET2_ENC_AES256)
+		return EINVAL;
+	if (ck->enc_key == nullptr || ck->enc_keylen != NET2_AES_KEYLEN)
+		return EINVAL;
+	if (ck->alt_enc_key != nullptr && ck->alt_enc_keylen != NET2_AES_KEYLEN)
+		return EINVAL;
+	return 0;
+}
+
 namespace {
 
 /* A workspace of an n-datagram burst (n <= UINT32_MAX): there, as large as
@@ -160,19 +173,6 @@ int check_burst_args(int hash_alg, const void *key, size_t keylen,
 	if (rc != 0 || n == 0)
 		return rc;
 	return burst_ws_ok(d_ws, ws_bytes, n) ? check_current_device() : EINVAL;
-}
-
-/* the cipher calls: aes256 with a 32-byte key, and as long an alternate key
- * or none */
-int check_cipher_keys(const struct net2_burst_cipher_keys *ck)
-{
-	if (ck == nullptr || ck->enc_alg != NET2_ENC_AES256)
-		return EINVAL;
-	if (ck->enc_key == nullptr || ck->enc_keylen != NET2_AES_KEYLEN)
-		return EINVAL;
-	if (ck->alt_enc_key != nullptr && ck->alt_enc_keylen != NET2_AES_KEYLEN)
-		return EINVAL;
-	return 0;
 }
 
 /* net2_sha2_burst_limits' two thresholds, net2_aes_burst_limits' one,
@@ -547,18 +547,7 @@ NET2_EXPORT int net2_packet_encrypt_burst(
 
 /* ---- keyed bursts over many connections: the device key table ------------- */
 
-/*
- * The table of include/net2/packet.h: `slots` entries (Net2KeyEnt,
- * sha2_launch.h) in the memory of the device that was current when it was
- * made, all of one HMAC row.  Entries change only through the set / clear
- * calls, each one launch in the caller's stream.
- */
-struct net2_burst_keytab {
-	int device;
-	int hash_alg;
-	uint32_t slots;
-	Net2KeyEnt *ents;
-};
+/* (struct net2_burst_keytab: net2_host.h) */
 
 /* Arguments first (by the caller), then: a usable device, and the table's. */
 int check_table_device(int device)
@@ -634,6 +623,8 @@ NET2_EXPORT void net2_burst_keytab_destroy(struct net2_burst_keytab *tab)
 {
 	if (tab == nullptr)
 		return;
+	/* the bulk updates' staging: its launches waited for, wiped, freed */
+	tab_stage_destroy(tab->stage);
 	/* (hipFree waits for the work that may still read the entries) */
 	(void)hipFree(tab->ents);
 	delete tab;
@@ -659,6 +650,7 @@ NET2_EXPORT int net2_burst_keytab_set_rx(struct net2_burst_keytab *tab,
 	    (const uint8_t *)keys->hash_key, (const uint8_t *)keys->alt_hash_key,
 	    keys->hash_keylen, bits, alt ? keys->alt_cutoff : 0,
 	    alt ? keys->rx_start : 0, (hipStream_t)stream));
+	tab_slot_launched();
 	return 0;
 }
 
@@ -674,6 +666,7 @@ NET2_EXPORT int net2_burst_keytab_set_tx(struct net2_burst_keytab *tab,
 	    (const uint8_t *)key, nullptr, keylen,
 	    NET2_KT_TX | (enc_alg != 0 ? NET2_KT_TX_ENC : 0), 0, 0,
 	    (hipStream_t)stream));
+	tab_slot_launched();
 	return 0;
 }
 
@@ -686,6 +679,7 @@ NET2_EXPORT int net2_burst_keytab_clear(struct net2_burst_keytab *tab,
 		return rc;
 	HIP_TRY(net2_launch_keytab_set(tab->hash_alg, tab->ents + slot, 0, nullptr,
 	    nullptr, 0, 0, 0, 0, (hipStream_t)stream));
+	tab_slot_launched();
 	return 0;
 }
 
@@ -799,17 +793,7 @@ NET2_EXPORT int net2_packet_encode_burst_mc(const struct net2_burst_keytab *tab,
 
 /* ---- the cipher under per-connection keys: the device cipher-key table ---- */
 
-/*
- * The cipher-key table of include/net2/packet.h: `slots` entries
- * (Net2CipherEnt, aes_tab.h) in the memory of the device that was current
- * when it was made.  Entries change only through the set / clear calls, each
- * one launch in the caller's stream.
- */
-struct net2_burst_ciphertab {
-	int device;
-	uint32_t slots;
-	Net2CipherEnt *ents;
-};
+/* (struct net2_burst_ciphertab: net2_host.h) */
 
 NET2_EXPORT int net2_burst_ciphertab_create(int enc_alg, uint32_t slots,
     struct net2_burst_ciphertab **tab)
@@ -855,6 +839,7 @@ NET2_EXPORT void net2_burst_ciphertab_destroy(struct net2_burst_ciphertab *tab)
 	if (prev != tab->device)
 		(void)hipSetDevice(tab->device);
 	(void)hipDeviceSynchronize();
+	tab_stage_destroy(tab->stage);
 	(void)hipMemset(tab->ents, 0, (size_t)tab->slots * NET2_AES_TAB_ENT_BYTES);
 	(void)hipFree(tab->ents);
 	if (prev >= 0 && prev != tab->device)
@@ -882,6 +867,7 @@ NET2_EXPORT int net2_burst_ciphertab_set_rx(struct net2_burst_ciphertab *tab,
 	    (const uint8_t *)ck->enc_key,
 	    alt ? (const uint8_t *)ck->alt_enc_key : nullptr, keys->alt_no_cutoff,
 	    keys->alt_cutoff, keys->rx_start, (hipStream_t)stream));
+	tab_slot_launched();
 	return 0;
 }
 
@@ -894,6 +880,7 @@ NET2_EXPORT int net2_burst_ciphertab_set_tx(struct net2_burst_ciphertab *tab,
 		return rc;
 	HIP_TRY(net2_launch_aes_tab_set(tab->ents, slot, NET2_AES_TAB_TX,
 	    (const uint8_t *)ck->enc_key, nullptr, 0, 0, 0, (hipStream_t)stream));
+	tab_slot_launched();
 	return 0;
 }
 
@@ -906,6 +893,7 @@ NET2_EXPORT int net2_burst_ciphertab_clear(struct net2_burst_ciphertab *tab,
 		return rc;
 	HIP_TRY(net2_launch_aes_tab_set(tab->ents, slot, 0, nullptr, nullptr, 0, 0,
 	    0, (hipStream_t)stream));
+	tab_slot_launched();
 	return 0;
 }
 

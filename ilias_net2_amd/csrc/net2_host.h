@@ -445,8 +445,35 @@ int encode_burst(int hash_alg, const void *hash_key, size_t hash_keylen,
  * aes_wave_form(n) (decrypt) and aes_quad_form(n) (encrypt).  seal_to as
  * encode_burst's.
  */
-struct net2_burst_keytab;
-struct net2_burst_ciphertab;
+struct Net2CipherEnt;
+struct TabStage;
+/*
+ * The two tables of include/net2/packet.h: `slots` entries (Net2KeyEnt,
+ * sha2_launch.h, all of one HMAC row; Net2CipherEnt, aes_tab.h) in the memory
+ * of the device that was current when the table was made.  Entries change
+ * only through the set / clear calls (net2_dgram.cpp), each one launch in the
+ * caller's stream, and through the bulk updates (net2_tabs.cpp), whose
+ * page-locked staging is `stage`, made by the first of them.
+ */
+struct net2_burst_keytab {
+	int device;
+	int hash_alg;
+	uint32_t slots;
+	Net2KeyEnt *ents;
+	TabStage *stage;
+};
+struct net2_burst_ciphertab {
+	int device;
+	uint32_t slots;
+	Net2CipherEnt *ents;
+	TabStage *stage;
+};
+/* Waits for the staging's launches, wipes and frees it (null: nothing). */
+void tab_stage_destroy(TabStage *st);
+/* net2_burst_tab_stats' count of per-slot launches (net2_tabs.cpp). */
+void tab_slot_launched();
+/* aes256 with a 32-byte key, and as long an alternate key or none */
+int check_cipher_keys(const struct net2_burst_cipher_keys *ck);
 int keytab_device(const struct net2_burst_keytab *tab);
 int keytab_hash_alg(const struct net2_burst_keytab *tab);
 int ciphertab_device(const struct net2_burst_ciphertab *tab);

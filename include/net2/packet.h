@@ -468,6 +468,108 @@ int net2_packet_encrypt_burst_mc(const struct net2_burst_ciphertab *tab,
     uint8_t *d_result, uint32_t *d_wire_len, void *stream);
 
 /*
+ * Bulk updates of the two tables: many slots in one call, the keys prepared
+ * on the device.  The per-slot calls above are right for one key commit
+ * between two bursts -- one launch each, the entry made on the host.  A
+ * server that loads its tables at start-up, or whose connections roll their
+ * keys over together, hands the whole list to one call here: the raw keys are
+ * staged, and one launch per at most ops_per_launch ops (default 65,536) has a
+ * lane per slot compute that slot's HMAC midstates or AES-256 schedules and
+ * store its entry.
+ *
+ * An op is one per-slot call: `op` NET2_BURST_TAB_RX takes exactly what
+ * _set_rx takes (key table: `rx`; cipher table: `rx` and `ck`),
+ * NET2_BURST_TAB_TX exactly what _set_tx takes (key table: tx_key, tx_keylen,
+ * tx_enc_alg; cipher table: `ck`), NET2_BURST_TAB_CLEAR is _clear; fields of
+ * the other ops are not looked at.
+ *
+ * Result: every entry of the table ends byte for byte as if the n per-slot
+ * calls had been issued in array order on `stream`.  Several ops on one slot
+ * apply in order, RX and TX of one slot both stay, a CLEAR undoes what came
+ * before it in the list and not what comes after.
+ * Ordering: asynchronous on `stream` and ordered with the bursts there, as
+ * the per-slot calls are -- a burst enqueued before the call sees the old
+ * entries, one enqueued after it the new ones; a host burst
+ * (net2_packet_*_burst_mc_host) sees an update queued on its table_stream
+ * before it.  Work on other streams is not ordered with it.
+ * Key lifetime: the keys are consumed before the call returns -- `ops` and
+ * everything they point to may be overwritten at once.  The library stages
+ * them in page-locked memory it owns (per table: a ring of areas, each
+ * reused once the launch that read it is done; a call waits on the host only
+ * while every area is in flight).  No raw key stays there once the update
+ * kernel has run -- each lane zeroes the record it read -- and the staging is
+ * wiped again and freed by _destroy.
+ * Capture: a `stream` that is being captured (hipStreamIsCapturing) is
+ * refused with EINVAL, since a graph cannot own the library's staging; the
+ * per-slot calls, whose entry travels in the launch's arguments, stay the
+ * form to capture.
+ *
+ * Every op is checked before any device work, in array order, each by the
+ * checks of its per-slot call: on the first bad one the call returns EINVAL,
+ * nothing is enqueued, no table byte and no counter changes.  EINVAL also for
+ * tab NULL, ops NULL with n > 0, an unknown `op`, n > UINT32_MAX, a capturing
+ * stream, and -- checked last -- a calling thread whose current device is not
+ * the table's; ENOMEM, ENODEV or EIO otherwise.  n == 0 is 0 and launches
+ * nothing.
+ */
+#define NET2_BURST_TAB_CLEAR 0u
+#define NET2_BURST_TAB_RX    1u
+#define NET2_BURST_TAB_TX    2u
+
+struct net2_burst_keytab_op {
+	uint32_t slot;
+	uint32_t op;                    /* NET2_BURST_TAB_{CLEAR,RX,TX} */
+	struct net2_burst_rx_keys rx;   /* RX: exactly net2_burst_keytab_set_rx's keys */
+	const void *tx_key;             /* TX: exactly net2_burst_keytab_set_tx's */
+	size_t tx_keylen;
+	int tx_enc_alg;
+};
+int net2_burst_keytab_update(struct net2_burst_keytab *tab,
+    const struct net2_burst_keytab_op *ops, size_t n, void *stream);
+
+struct net2_burst_ciphertab_op {
+	uint32_t slot;
+	uint32_t op;
+	struct net2_burst_rx_keys rx;        /* RX: set_rx's `keys` (the alternate-key state) */
+	struct net2_burst_cipher_keys ck;    /* RX: set_rx's `ck`; TX: set_tx's `ck` */
+};
+int net2_burst_ciphertab_update(struct net2_burst_ciphertab *tab,
+    const struct net2_burst_ciphertab_op *ops, size_t n, void *stream);
+
+/*
+ * The most ops one launch of a bulk update takes, process-wide (a test knob,
+ * like net2_aes_burst_limits): a longer list is cut into launches that keep
+ * their order.  A value < 0 restores the default, 65,536; 0 counts as 1.
+ * Results do not depend on it.  Always 0; needs no device.
+ */
+int net2_burst_tab_limits(int64_t ops_per_launch);
+
+/*
+ * Table-update launches of this process so far (either pointer may be NULL):
+ * those of the per-slot calls of both tables, and those of the bulk updates.
+ * A call refused by its argument checks launches nothing.  Host state, needs
+ * no device.  Always 0.
+ */
+int net2_burst_tab_stats(uint64_t *slot_launches, uint64_t *bulk_launches);
+
+/*
+ * Fingerprints of table entries: the SHA-256 of each of the n entries from
+ * slot `first`, 32 bytes per slot, to d_digests (device memory), asynchronous
+ * on `stream` and ordered with the updates there.  Two tables that hold the
+ * same keys and state have the same fingerprints, so an operator compares
+ * replicas -- and a test a bulk-filled table with a per-slot-filled one --
+ * without key material leaving the device.  (A slot's fingerprint covers the
+ * whole entry, also the bytes a key-table CLEAR leaves behind.)
+ * 0, EINVAL (tab NULL, first + n > slots, d_digests NULL with n > 0, or --
+ * checked last -- a calling thread whose device is not the table's), ENODEV
+ * or EIO; n == 0 is 0.
+ */
+int net2_burst_keytab_fingerprint(const struct net2_burst_keytab *tab,
+    uint32_t first, uint32_t n, void *d_digests, void *stream);
+int net2_burst_ciphertab_fingerprint(const struct net2_burst_ciphertab *tab,
+    uint32_t first, uint32_t n, void *d_digests, void *stream);
+
+/*
  * Host-memory bursts: the same hash steps for datagrams that live in host
  * memory -- the reference's case: each received one is a net2_buffer filled
  * by net2_sockdgram_recv (src/sockdgram.c:67-108) and decoded at
