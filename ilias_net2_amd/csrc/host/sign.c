@@ -270,3 +270,161 @@ net2x_signctx_fingerprint(struct net2x_sign_ctx *s, uint8_t out[32])
 	pthread_mutex_unlock(&s->mu);
 	return rc;
 }
+
+/* ---- batched validation on the device (net2/ecdsa.h) ----------------------- */
+
+#include "../../../include/net2/ecdsa.h"
+#include "signature_int.h"
+
+#include <openssl/ecdsa.h>
+#include <openssl/obj_mac.h>
+
+#define P521_BYTES 66
+
+/* Is the context's key on secp521r1, the curve the device verifies? */
+int
+signctx_is_p521(struct net2x_sign_ctx *s)
+{
+	const EC_KEY *ek;
+	const EC_GROUP *g;
+
+	return s != NULL && (ek = EVP_PKEY_get0_EC_KEY(s->pkey)) != NULL &&
+	    (g = EC_KEY_get0_group(ek)) != NULL &&
+	    EC_GROUP_get_curve_name(g) == NID_secp521r1;
+}
+
+/*
+ * What ECDSA_verify does with a signature before the mathematics
+ * (crypto/ec/ecdsa_vrf.c): parse the DER, re-encode it, and refuse anything
+ * that is not byte for byte its own canonical encoding -- trailing bytes,
+ * non-minimal lengths.  d2i accepts a negative INTEGER, which the
+ * verification then refuses; so is it here, as is a value too long for the
+ * 66-byte form (both are outside [1, n - 1]).  1 with r || s in rs, else 0.
+ */
+static int
+der_to_rs(const uint8_t *sig, size_t siglen, uint8_t rs[2 * P521_BYTES])
+{
+	const unsigned char *p = sig;
+	unsigned char *der = NULL;
+	const BIGNUM *r, *s;
+	ECDSA_SIG *es;
+	int derlen, ok = 0;
+
+	if (sig == NULL || siglen == 0 || siglen > INT32_MAX ||
+	    (es = d2i_ECDSA_SIG(NULL, &p, (long)siglen)) == NULL)
+		return 0;
+	derlen = i2d_ECDSA_SIG(es, &der);
+	if (derlen > 0 && (size_t)derlen == siglen &&
+	    memcmp(sig, der, siglen) == 0) {
+		ECDSA_SIG_get0(es, &r, &s);
+		ok = !BN_is_negative(r) && !BN_is_negative(s) &&
+		    BN_num_bytes(r) <= P521_BYTES && BN_num_bytes(s) <= P521_BYTES &&
+		    BN_bn2binpad(r, rs, P521_BYTES) == P521_BYTES &&
+		    BN_bn2binpad(s, rs + P521_BYTES, P521_BYTES) == P521_BYTES;
+	}
+	OPENSSL_free(der);
+	ECDSA_SIG_free(es);
+	return ok;
+}
+
+/* x || y of the context's key, from its cached uncompressed point */
+static int
+signctx_xy(struct net2x_sign_ctx *s, uint8_t xy[2 * P521_BYTES])
+{
+	int rc;
+
+	pthread_mutex_lock(&s->mu);
+	rc = pubkey_cached(s);
+	if (rc == 0 && (s->publen != 1 + 2 * P521_BYTES || s->pub[0] != 0x04))
+		rc = EINVAL;
+	if (rc == 0)
+		memcpy(xy, s->pub + 1, 2 * P521_BYTES);
+	pthread_mutex_unlock(&s->mu);
+	return rc;
+}
+
+/*
+ * n DER signatures on the device: item i under ctxs[i * ctx_step] (step 0:
+ * one context for all), its digest at digests + i * dig_stride, dlens[i]
+ * bytes (or dlen where dlens is NULL).  Every context is on P-521 (the
+ * callers looked).  The signatures the host part settles never reach the
+ * device; the rest go in one net2_ecdsa_p521_verify batch.
+ */
+int
+signctx_validate_batch_dev(struct net2x_sign_ctx *const *ctxs, size_t ctx_step,
+    const uint8_t *const *sigs, const size_t *siglens, const uint8_t *digests,
+    size_t dig_stride, const uint32_t *dlens, uint32_t dlen, size_t n,
+    int *valid)
+{
+	uint8_t *pub = NULL, *rs = NULL, *dig = NULL, *verdict = NULL;
+	uint32_t *lens = NULL;
+	size_t *at = NULL, m = 0, width = dlen;
+	int rc = 0;
+
+	for (size_t i = 0; i < n; i++) {
+		valid[i] = 0;
+		if (dlens != NULL && dlens[i] > width)
+			width = dlens[i];
+	}
+	if (width == 0)
+		width = 1;
+	pub = malloc((ctx_step ? n : 1) * 2 * P521_BYTES);
+	rs = malloc(n * 2 * P521_BYTES);
+	dig = malloc(n * width);
+	lens = malloc(n * sizeof(*lens));
+	at = malloc(n * sizeof(*at));
+	verdict = calloc(n, 1);
+	if (!pub || !rs || !dig || !lens || !at || !verdict) {
+		rc = ENOMEM;
+		goto out;
+	}
+	if (ctx_step == 0 && (rc = signctx_xy(ctxs[0], pub)) != 0)
+		goto out;
+	for (size_t i = 0; i < n; i++) {
+		struct net2x_sign_ctx *s = ctxs[i * ctx_step];
+		const uint32_t dl = dlens != NULL ? dlens[i] : dlen;
+
+		if (sigs[i] == NULL || siglens[i] > net2x_signctx_maxmsglen(s) ||
+		    dl > dig_stride || !der_to_rs(sigs[i], siglens[i],
+		    rs + m * 2 * P521_BYTES))
+			continue;		/* valid[i] stays 0 */
+		if (ctx_step != 0 &&
+		    (rc = signctx_xy(s, pub + m * 2 * P521_BYTES)) != 0)
+			goto out;
+		if (dl > 0)
+			memcpy(dig + m * width, digests + i * dig_stride, dl);
+		lens[m] = dl;
+		at[m++] = i;
+	}
+	if (m > 0) {
+		rc = net2_ecdsa_p521_verify(pub, ctx_step ? 2 * P521_BYTES : 0, rs,
+		    dig, width, lens, 0, m, verdict);
+		for (size_t k = 0; rc == 0 && k < m; k++)
+			valid[at[k]] = verdict[k] == 1;
+	}
+out:
+	free(pub);
+	free(rs);
+	free(dig);
+	free(lens);
+	free(at);
+	free(verdict);
+	return rc;
+}
+
+NET2_EXPORT int
+net2x_signctx_validate_batch(struct net2x_sign_ctx *s,
+    const uint8_t *const *sigs, const size_t *siglens, const uint8_t *digests,
+    size_t dig_stride, size_t dlen, size_t n, int *valid)
+{
+	if (n == 0)
+		return 0;
+	if (s == NULL || sigs == NULL || siglens == NULL || valid == NULL ||
+	    (digests == NULL && dlen > 0) || dlen > UINT32_MAX ||
+	    (n > 1 && dig_stride < dlen))
+		return EINVAL;
+	if (!signctx_is_p521(s))
+		return EOPNOTSUPP;
+	return signctx_validate_batch_dev(&s, 0, sigs, siglens, digests,
+	    n > 1 ? dig_stride : dlen, NULL, (uint32_t)dlen, n, valid);
+}

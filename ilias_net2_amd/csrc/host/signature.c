@@ -7,7 +7,8 @@
  * The digest of every payload comes from the MI355X path
  * (net2_hashctx_hashiov for one payload, net2_sha2_batch for a batch); the
  * ECDSA step stays on the host (OpenSSL), spread over a few threads in the
- * batched forms.
+ * batched forms -- except in net2x_signature_validate_batch_dev, whose
+ * verifications run on the device too (net2/ecdsa.h).
  */
 #include "../../../include/net2/signature.h"
 #include "../../../include/net2/hash.h"
@@ -319,5 +320,104 @@ out:
 	free(sub_len);
 	free(digests);
 	free(sub_dig);
+	return rc;
+}
+
+/*
+ * net2x_signature_validate_batch with the verification on the device: the
+ * same prologue and the same hash batches, then every signature that names
+ * the context's algorithm goes into one signctx_validate_batch_dev call
+ * with its own digest length.
+ */
+NET2_EXPORT int
+net2x_signature_validate_batch_dev(const struct net2x_signature *sigs,
+    const uint8_t *base, const uint64_t *offsets, const uint32_t *lens,
+    size_t n, struct net2x_sign_ctx *sign, int *valid)
+{
+	int *alg_of = NULL, *sub_valid = NULL;
+	size_t *idx = NULL, m;
+	uint64_t *sub_off = NULL;
+	uint32_t *sub_len = NULL, *dlens = NULL;
+	uint8_t *digests = NULL, *sub_dig = NULL;
+	const uint8_t **der = NULL;
+	size_t *derlen = NULL;
+	int rc = 0;
+
+	if (n == 0)
+		return 0;
+	if (sigs == NULL || offsets == NULL || lens == NULL || sign == NULL ||
+	    valid == NULL)
+		return EINVAL;
+	if (!signctx_is_p521(sign))
+		return EOPNOTSUPP;
+	alg_of = malloc(n * sizeof(*alg_of));
+	sub_valid = malloc(n * sizeof(*sub_valid));
+	idx = malloc(n * sizeof(*idx));
+	sub_off = malloc(n * sizeof(*sub_off));
+	sub_len = malloc(n * sizeof(*sub_len));
+	dlens = malloc(n * sizeof(*dlens));
+	digests = malloc(n * 64);
+	sub_dig = malloc(n * 64);
+	der = malloc(n * sizeof(*der));
+	derlen = malloc(n * sizeof(*derlen));
+	if (!alg_of || !sub_valid || !idx || !sub_off || !sub_len || !dlens ||
+	    !digests || !sub_dig || !der || !derlen) {
+		rc = ENOMEM;
+		goto out;
+	}
+	for (size_t i = 0; i < n; i++) {
+		int v;
+		alg_of[i] = validate_prologue(&sigs[i], &v);
+		valid[i] = 0;
+	}
+	/* one GPU batch per hash algorithm named by the signatures */
+	for (int alg = 1; alg < net2_hashmax && rc == 0; alg++) {
+		int hl = net2_hash_gethashlen(alg);
+		m = 0;
+		for (size_t i = 0; i < n; i++)
+			if (alg_of[i] == alg) {
+				idx[m] = i;
+				sub_off[m] = offsets[i];
+				sub_len[m] = lens[i];
+				m++;
+			}
+		if (m == 0)
+			continue;
+		rc = net2_sha2_batch(alg, base, sub_off, sub_len, 0, 0, m,
+		    sub_dig, 0);
+		for (size_t k = 0; rc == 0 && k < m; k++)
+			memcpy(digests + idx[k] * 64, sub_dig + k * hl, (size_t)hl);
+	}
+	if (rc != 0)
+		goto out;
+	/* ... and one verification batch, packed: digest k in slot k */
+	m = 0;
+	for (size_t i = 0; i < n; i++) {
+		if (alg_of[i] < 0 ||
+		    strcmp(net2x_signctx_name(sign), sigs[i].sign_alg) != 0)
+			continue;	/* valid[i] stays 0 */
+		idx[m] = i;
+		der[m] = sigs[i].data;
+		derlen[m] = sigs[i].datalen;
+		dlens[m] = (uint32_t)net2_hash_gethashlen(alg_of[i]);
+		memmove(digests + m * 64, digests + i * 64, 64);
+		m++;
+	}
+	if (m > 0)
+		rc = signctx_validate_batch_dev(&sign, 0, der, derlen, digests, 64,
+		    dlens, 0, m, sub_valid);
+	for (size_t k = 0; rc == 0 && k < m; k++)
+		valid[idx[k]] = sub_valid[k];
+out:
+	free(alg_of);
+	free(sub_valid);
+	free(idx);
+	free(sub_off);
+	free(sub_len);
+	free(dlens);
+	free(digests);
+	free(sub_dig);
+	free(der);
+	free(derlen);
 	return rc;
 }

@@ -360,6 +360,7 @@ struct ecdsa_plan {
 	const uint8_t			*sdig;	/* ns x 64 */
 	const uint8_t			*vdig;	/* nv x 64 */
 	const int			*valg;	/* hash row per check, < 0 bad */
+	const uint8_t			*vdev;	/* per check: settled on the device */
 	const size_t			*sjob;	/* prefix sums of num_signatures */
 	size_t				 nsig_jobs, njobs;
 };
@@ -415,7 +416,8 @@ ecdsa_run(void *arg)
 		}
 		const size_t v = j - pl->nsig_jobs;
 		struct net2_sc_validate_req *q = &pl->vreq[v];
-		if (pl->valg[v] < 0 || q->result != 0)
+		if (pl->valg[v] < 0 || q->result != 0 ||
+		    (pl->vdev != NULL && pl->vdev[v]))
 			continue;
 		if (strcmp(net2x_signctx_name(q->sctx), q->sig->sign_alg) != 0) {
 			q->result = EIO;	/* signature.n2t:155-158 -> :333-336 */
@@ -479,13 +481,69 @@ hash_req_ok(const struct net2_sc_hash_req *h)
 	    net2_hash_getkeylen(h->hash_alg) == 0;
 }
 
+/*
+ * The checks of a tick that can be verified on the device -- hashed, naming
+ * their context's algorithm, the context on secp521r1 -- in one batch with
+ * one key per check (signctx_validate_batch_dev).  vdev[v] = 1 marks a check
+ * settled here, so the host threads leave it alone; a batch that could not
+ * run settles its checks as EIO (could not be validated).
+ */
+static void
+validate_on_device(struct net2_sc_validate_req *vreq, size_t nv,
+    const int *valg, const uint8_t *vdig, uint8_t *vdev)
+{
+	struct net2x_sign_ctx **ctxs = malloc((nv + 1) * sizeof(*ctxs));
+	const uint8_t **der = malloc((nv + 1) * sizeof(*der));
+	size_t *derlen = malloc((nv + 1) * sizeof(*derlen));
+	size_t *at = malloc((nv + 1) * sizeof(*at)), m = 0;
+	uint32_t *dlens = malloc((nv + 1) * sizeof(*dlens));
+	uint8_t *dig = malloc(nv * 64 + 1);
+	int *valid = malloc((nv + 1) * sizeof(*valid));
+	int rc = ctxs && der && derlen && at && dlens && dig && valid ? 0 : ENOMEM;
+
+	for (size_t v = 0; v < nv; v++) {
+		struct net2_sc_validate_req *q = &vreq[v];
+
+		if (valg[v] < 0 || q->result != 0 || !signctx_is_p521(q->sctx) ||
+		    strcmp(net2x_signctx_name(q->sctx), q->sig->sign_alg) != 0)
+			continue;	/* the host threads' */
+		vdev[v] = 1;
+		if (rc != 0)
+			continue;
+		ctxs[m] = q->sctx;
+		der[m] = q->sig->data;
+		derlen[m] = q->sig->datalen;
+		dlens[m] = (uint32_t)net2_hash_gethashlen(valg[v]);
+		memcpy(dig + 64 * m, vdig + 64 * v, 64);
+		at[m++] = v;
+	}
+	if (rc == 0 && m > 0)
+		rc = signctx_validate_batch_dev(ctxs, 1, der, derlen, dig, 64, dlens,
+		    0, m, valid);
+	if (rc == 0) {
+		for (size_t k = 0; k < m; k++)
+			vreq[at[k]].result = valid[k] == 1 ? 0 : EINVAL;
+	} else {
+		for (size_t v = 0; v < nv; v++)
+			if (vdev[v])
+				vreq[v].result = EIO;
+	}
+	free(ctxs);
+	free(der);
+	free(derlen);
+	free(at);
+	free(dlens);
+	free(dig);
+	free(valid);
+}
+
 static int
 tick(struct net2_sc_hash_req **hreq, size_t nh,
     struct net2_sc_sign_req *sreq, size_t ns,
-    struct net2_sc_validate_req *vreq, size_t nv, int nthreads)
+    struct net2_sc_validate_req *vreq, size_t nv, int nthreads, int dev)
 {
 	struct payload_ref *p = NULL;
-	uint8_t *sdig = NULL, *vdig = NULL;
+	uint8_t *sdig = NULL, *vdig = NULL, *vdev = NULL;
 	int *valg = NULL, rc = 0;
 	size_t *sjob = NULL, np = 0;
 	struct ecdsa_plan pl;
@@ -501,8 +559,9 @@ tick(struct net2_sc_hash_req **hreq, size_t nh,
 	vdig = malloc(nv * 64 + 1);
 	valg = malloc((nv + 1) * sizeof(*valg));
 	sjob = malloc((ns + 1) * sizeof(*sjob));
+	vdev = dev ? calloc(nv + 1, 1) : NULL;
 	if (p == NULL || sdig == NULL || vdig == NULL || valg == NULL ||
-	    sjob == NULL) {
+	    sjob == NULL || (dev && vdev == NULL)) {
 		rc = ENOMEM;
 		for (size_t i = 0; i < ns; i++)
 			sreq[i].rc = ENOMEM;
@@ -558,7 +617,11 @@ tick(struct net2_sc_hash_req **hreq, size_t nh,
 		if (hreq[i]->rc == 0)
 			hreq[i]->digestlen =
 			    (uint32_t)net2_hash_gethashlen(hreq[i]->hash_alg);
+	/* the checks the device can verify, in one batch */
+	if (dev)
+		validate_on_device(vreq, nv, valg, vdig, vdev);
 	/* the callbacks and the ECDSA work on host threads */
+	pl.vdev = vdev;
 	pl.hreq = hreq;
 	pl.nh = nh;
 	pl.sreq = sreq;
@@ -611,6 +674,7 @@ out:
 	free(vdig);
 	free(valg);
 	free(sjob);
+	free(vdev);
 	return rc;
 }
 
@@ -635,7 +699,7 @@ net2_sc_hash_tick(struct net2_sc_hash_req *reqs, size_t n, int nthreads)
 	}
 	for (size_t i = 0; i < n; i++)
 		hp[i] = &reqs[i];
-	rc = tick(hp, n, NULL, 0, NULL, 0, nthreads);
+	rc = tick(hp, n, NULL, 0, NULL, 0, nthreads, 0);
 	free(hp);
 	return rc;
 }
@@ -646,7 +710,7 @@ net2_signed_carver_sign_tick(struct net2_sc_sign_req *reqs, size_t n,
 {
 	if (n > 0 && reqs == NULL)
 		return EINVAL;
-	return tick(NULL, 0, reqs, n, NULL, 0, nthreads);
+	return tick(NULL, 0, reqs, n, NULL, 0, nthreads, 0);
 }
 
 NET2_EXPORT int
@@ -655,7 +719,16 @@ net2_signed_combiner_validate_tick(struct net2_sc_validate_req *reqs,
 {
 	if (n > 0 && reqs == NULL)
 		return EINVAL;
-	return tick(NULL, 0, NULL, 0, reqs, n, nthreads);
+	return tick(NULL, 0, NULL, 0, reqs, n, nthreads, 0);
+}
+
+NET2_EXPORT int
+net2_signed_combiner_validate_tick_dev(struct net2_sc_validate_req *reqs,
+    size_t n, int nthreads)
+{
+	if (n > 0 && reqs == NULL)
+		return EINVAL;
+	return tick(NULL, 0, NULL, 0, reqs, n, nthreads, 1);
 }
 
 /* ---- the collector ---------------------------------------------------- */
@@ -809,7 +882,7 @@ net2_sc_collector_tick(struct net2_sc_collector *c, size_t *nhash,
 		sreq[i] = *sp[i];
 	for (size_t i = 0; i < nv; i++)
 		vreq[i] = *vp[i];
-	rc = tick(hp, nh, sreq, ns, vreq, nv, c->nthreads);
+	rc = tick(hp, nh, sreq, ns, vreq, nv, c->nthreads, 0);
 	for (size_t i = 0; i < ns; i++)
 		sp[i]->rc = sreq[i].rc;
 	for (size_t i = 0; i < nv; i++)

@@ -15,7 +15,9 @@
  *
  * ECDSA (the reference's only algorithm, src/sign.c:164-166) runs on the
  * host through OpenSSL exactly as src/sign.c:478-563 does (the digest is
- * signed as is, DER ECDSA-Sig out).  The one SHA-2 use of src/sign.c, the
+ * signed as is, DER ECDSA-Sig out); verification of a whole batch under a
+ * P-521 key can also run on the MI355X with the same verdicts
+ * (net2x_signctx_validate_batch).  The one SHA-2 use of src/sign.c, the
  * public-key fingerprint (src/sign.c:258-320), is computed by the MI355X
  * path (net2_hashctx_hashiov).
  */
@@ -64,6 +66,22 @@ int net2x_signctx_sign(struct net2x_sign_ctx *, const void *in, size_t inlen,
  * 518-563). */
 int net2x_signctx_validate(struct net2x_sign_ctx *, const void *sig,
     size_t siglen, const void *in, size_t inlen);
+
+/*
+ * n DER signatures of one context over n digests (digest i at digests +
+ * i * dig_stride, dlen bytes each), verified on the MI355X
+ * (net2_ecdsa_p521_verify, net2/ecdsa.h); valid[i] = 1 / 0 with
+ * net2x_signctx_validate's meaning.  The host does what ECDSA_verify does
+ * before the mathematics -- a signature longer than
+ * net2x_signctx_maxmsglen, one that is not exactly its own canonical DER,
+ * or an r or s that is negative or longer than 66 bytes is invalid without
+ * reaching the device.  0; EINVAL; EOPNOTSUPP when the context's curve is not
+ * secp521r1 (the caller keeps net2x_signctx_validate on its threads); else
+ * the errno of the device call (ENODEV: there is no CPU fallback here).
+ */
+int net2x_signctx_validate_batch(struct net2x_sign_ctx *,
+    const uint8_t *const *sigs, const size_t *siglens, const uint8_t *digests,
+    size_t dig_stride, size_t dlen, size_t n, int *valid);
 
 const char *net2x_signctx_name(struct net2x_sign_ctx *);
 

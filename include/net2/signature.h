@@ -69,6 +69,17 @@ int net2x_signature_validate_batch(const struct net2x_signature *sigs,
     const uint8_t *base, const uint64_t *offsets, const uint32_t *lens,
     size_t n, struct net2x_sign_ctx *sign, int *valid, int nthreads);
 
+/*
+ * net2x_signature_validate_batch with the ECDSA step on the MI355X as well
+ * (net2x_signctx_validate_batch): one GPU hash batch per algorithm as there,
+ * then one verification batch; valid[] is the same.  EOPNOTSUPP when the
+ * context's curve is not secp521r1, else as there plus the errno of the
+ * device verification.
+ */
+int net2x_signature_validate_batch_dev(const struct net2x_signature *sigs,
+    const uint8_t *base, const uint64_t *offsets, const uint32_t *lens,
+    size_t n, struct net2x_sign_ctx *sign, int *valid);
+
 #ifdef __cplusplus
 }
 #endif

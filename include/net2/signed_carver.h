@@ -121,6 +121,16 @@ int net2_signed_carver_sign_tick(struct net2_sc_sign_req *reqs, size_t n,
 int net2_signed_combiner_validate_tick(struct net2_sc_validate_req *reqs,
     size_t n, int nthreads);
 
+/*
+ * The same with the checks under secp521r1 contexts verified on the MI355X
+ * in one batch (net2_ecdsa_p521_verify with one key per check); the checks
+ * under other curves run on the host threads as above.  result per request
+ * has the same meaning; a device verification that could not run leaves EIO
+ * in its checks.
+ */
+int net2_signed_combiner_validate_tick_dev(struct net2_sc_validate_req *reqs,
+    size_t n, int nthreads);
+
 /* The collector: add from any thread, tick from one. */
 struct net2_sc_collector;
 
