@@ -10,6 +10,7 @@
 #define OPENSSL_SUPPRESS_DEPRECATED	/* EC_KEY point export, as sign.c */
 #include "../../../include/net2/sign.h"
 #include "../../../include/net2/hash.h"
+#include "../../../include/net2/ecdsa_key.h"
 
 #include <errno.h>
 #include <pthread.h>
@@ -33,6 +34,9 @@ struct net2x_sign_ctx {
 	size_t		 publen;
 	int		 have_fp;
 	uint8_t		 fp[32];	/* cached fingerprint */
+	/* the key prepared for the device (net2x_signctx_prepare_dev), or NULL;
+	 * set once under mu, freed with the context */
+	struct net2_ecdsa_p521_keys *keys;
 };
 
 static const char *const sign_names[] = { "ecdsa" };
@@ -112,6 +116,7 @@ net2x_signctx_free(struct net2x_sign_ctx *s)
 		return;
 	EVP_PKEY_free(s->pkey);
 	free(s->pub);
+	net2_ecdsa_p521_keys_free(s->keys);
 	pthread_mutex_destroy(&s->mu);
 	free(s);
 }
@@ -348,7 +353,9 @@ signctx_xy(struct net2x_sign_ctx *s, uint8_t xy[2 * P521_BYTES])
  * one context for all), its digest at digests + i * dig_stride, dlens[i]
  * bytes (or dlen where dlens is NULL).  Every context is on P-521 (the
  * callers looked).  The signatures the host part settles never reach the
- * device; the rest go in one net2_ecdsa_p521_verify batch.
+ * device; the rest go in one net2_ecdsa_p521_verify batch -- or, for one
+ * context that was prepared (net2x_signctx_prepare_dev), in one
+ * net2_ecdsa_p521_verify_keys batch from its key's table.
  */
 int
 signctx_validate_batch_dev(struct net2x_sign_ctx *const *ctxs, size_t ctx_step,
@@ -397,8 +404,19 @@ signctx_validate_batch_dev(struct net2x_sign_ctx *const *ctxs, size_t ctx_step,
 		at[m++] = i;
 	}
 	if (m > 0) {
-		rc = net2_ecdsa_p521_verify(pub, ctx_step ? 2 * P521_BYTES : 0, rs,
-		    dig, width, lens, 0, m, verdict);
+		const struct net2_ecdsa_p521_keys *keys = NULL;
+
+		if (ctx_step == 0) {
+			pthread_mutex_lock(&ctxs[0]->mu);
+			keys = ctxs[0]->keys;
+			pthread_mutex_unlock(&ctxs[0]->mu);
+		}
+		if (keys != NULL)	/* prepared: through the key's table */
+			rc = net2_ecdsa_p521_verify_keys(keys, NULL, rs, dig, width,
+			    lens, 0, m, verdict);
+		else
+			rc = net2_ecdsa_p521_verify(pub, ctx_step ? 2 * P521_BYTES : 0,
+			    rs, dig, width, lens, 0, m, verdict);
 		for (size_t k = 0; rc == 0 && k < m; k++)
 			valid[at[k]] = verdict[k] == 1;
 	}
@@ -409,6 +427,33 @@ out:
 	free(lens);
 	free(at);
 	free(verdict);
+	return rc;
+}
+
+NET2_EXPORT int
+net2x_signctx_prepare_dev(struct net2x_sign_ctx *s)
+{
+	uint8_t xy[2 * P521_BYTES], ok = 0;
+	struct net2_ecdsa_p521_keys *keys = NULL;
+	int rc;
+
+	if (s == NULL)
+		return EINVAL;
+	if (!signctx_is_p521(s))
+		return EOPNOTSUPP;
+	if ((rc = signctx_xy(s, xy)) != 0)
+		return rc;
+	pthread_mutex_lock(&s->mu);
+	if (s->keys == NULL) {
+		rc = net2_ecdsa_p521_keys_new(xy, sizeof(xy), 1, &keys, &ok);
+		if (rc == 0 && ok != 1) {	/* OpenSSL loaded it: cannot be */
+			net2_ecdsa_p521_keys_free(keys);
+			rc = EINVAL;
+		} else if (rc == 0) {
+			s->keys = keys;
+		}
+	}
+	pthread_mutex_unlock(&s->mu);
 	return rc;
 }
 

@@ -83,6 +83,20 @@ int net2x_signctx_validate_batch(struct net2x_sign_ctx *,
     const uint8_t *const *sigs, const size_t *siglens, const uint8_t *digests,
     size_t dig_stride, size_t dlen, size_t n, int *valid);
 
+/*
+ * Prepares the context's key for the device once (a one-key
+ * net2_ecdsa_p521_keys, net2/ecdsa_key.h, on the calling thread's selected
+ * device), kept in the context until net2x_signctx_free.  From then on
+ * net2x_signctx_validate_batch and net2x_signature_validate_batch_dev verify
+ * through the key's table: the same verdicts, without the per-signature
+ * doublings.  Worth it for a key that verifies more than a few hundred
+ * signatures.  Calling it again is a no-op; a clone starts unprepared; a
+ * context that was never prepared behaves as before.  0; EINVAL;
+ * EOPNOTSUPP when the curve is not secp521r1; else the errno of
+ * net2_ecdsa_p521_keys_new (ENODEV: no device).
+ */
+int net2x_signctx_prepare_dev(struct net2x_sign_ctx *);
+
 const char *net2x_signctx_name(struct net2x_sign_ctx *);
 
 /*
